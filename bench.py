@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — FRI commit throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up,
+W warm-up steps, K timed steps, the outputs of the last timed step written to
+DIR when --dump-outputs is given, one JSON line.  Everything else the bench
+measures or checks runs only with --full: the comparison of the transcript
+with the C oracle's golden one, the dominant kernel's roofline and the
+per-phase breakdown (profiled steps of their own), the serving / PCIe /
+decommit / prover / 2^28 side stages, the N > 1 secondary scaling points and
+the CPU baselines; --no-profile, --no-extras, --no-secondary and
+--no-cpu-baseline take single parts out of a --full run.
 
 One step = one full FRI commit (src/fri/fri_commit.rs:72-122) of a synthetic
 random polynomial with d = 2^21 coefficients (blowup 8) onto the codeword
@@ -15,9 +25,9 @@ N > 1 (torchrun, one process per GPU): by default strong scaling of ONE
 ranks (fri_commit_sharded_device over the library's RCCL communicator), with
 the weak 2^24-per-GPU and the strong 2^24 points as secondary keys
 (`scaling_points`); `--log-n L` alone selects weak scaling, 2^L per GPU.
-The sharded transcript is checked against the C oracle's golden transcript
-(tests/golden/bench_transcripts.json) before timing; on any mismatch/error
-every rank falls back to --mode replicas (N independent commits) and
+With --full the sharded transcript is checked against the C oracle's golden
+transcript (tests/golden/bench_transcripts.json) before timing; on any
+mismatch (--full) or error every rank falls back to --mode replicas (N independent commits) and
 `config.parallelism` says so.  value = codeword elements committed per second
 by the whole job, timed by the slowest rank.
 
@@ -156,7 +166,7 @@ def _host_transport_check(fri_amd, ctx, dist, world, rank, logG, args, agree, ti
     for L in points:
         dL = 1 << (L - args.blowup_log)
         cf = _coeffs(42, dL, fri_amd.P)
-        exp = _expected(L, args.blowup_log)
+        exp = _expected(L, args.blowup_log, args.full)
         got = {}
 
         def first():
@@ -178,9 +188,12 @@ def _host_transport_check(fri_amd, ctx, dist, world, rank, logG, args, agree, ti
     return out
 
 
-def _expected(log_n, blowup_log):
+def _expected(log_n, blowup_log, full=True):
     """Oracle transcript of the bench workload (tests/golden/bench_transcripts.json,
-    written by tests/golden/make_bench_transcripts.py from the C oracle), or None."""
+    written by tests/golden/make_bench_transcripts.py from the C oracle), or None;
+    None in a run without --full (`full` False), which compares with no reference."""
+    if not full:
+        return None
     try:
         with open(os.path.join(ROOT, "tests", "golden", "bench_transcripts.json")) as f:
             return json.load(f).get(f"{log_n}/42/{blowup_log}")
@@ -277,7 +290,18 @@ def main():
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the side measurements (PCIe-inclusive, serving, prover, 2^28): A/B timing runs")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the transcript checked against the C oracle's, roofline and "
+                         "per-phase breakdown, side stages, secondary scaling points and CPU baselines "
+                         "(each --no-* flag takes its part out again); a run without --full has none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (and, N=1, a fixed sample "
+                         "of its resident layers) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_profile = args.no_extras = True
     plan = launch_plan(args.gpus, os.environ, args.transport)
     if plan == "spawn":
         os.dup2(json_fd, 1)                         # the relayed line goes to the real stdout
@@ -325,7 +349,7 @@ def main():
             _team_wait(pg)
             return
         dist = None
-    ndev_all = _device_count()
+    ndev_all = _device_count() if (team_n or world > 1) else 1     # one process on one GPU: no use for the count
     logG = (team_n or world).bit_length() - 1
     mode = args.mode if (team_n or world) > 1 else "single"
     if (team_n or world) > 1 and (1 << logG) != (team_n or world):
@@ -414,7 +438,7 @@ def main():
                 break
             dL = 1 << (L - args.blowup_log)
             cf = _coeffs(42, dL, fri_amd.P)                     # one polynomial for the whole job
-            exp = _expected(L, args.blowup_log)
+            exp = _expected(L, args.blowup_log, args.full)
             first = fri_amd.CommitResult()
 
             def first_commit():
@@ -520,7 +544,7 @@ def main():
         ctx = fri_amd.Context(device, log_n)
         coeffs = _coeffs(42 + (rank if mode == "replicas" else 0), d, fri_amd.P)   # replicas: a codeword per rank
         res0 = ctx.commit(coeffs, log_n)
-        exp = _expected(log_n, args.blowup_log) if mode == "single" else None
+        exp = _expected(log_n, args.blowup_log, args.full) if mode == "single" else None
         verified = exp is not None and _matches(res0, exp)
         if exp is not None and not verified:
             raise SystemExit("1-GPU transcript differs from the C oracle's (tests/golden/bench_transcripts.json)")
@@ -536,6 +560,8 @@ def main():
     elapsed = timed(step, args.steps, args.warmup)
     if args.warmup:
         assert _same(res, res0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, ctx if mode == "single" else None, log_n)
 
     n = 1 << log_n
     ms_per_step = 1000.0 * elapsed / args.steps
@@ -777,7 +803,8 @@ def main():
             "config": {"workload": workload, "codeword_log2": log_n, "per_gpu_log2": blk_log,
                        "blowup": 1 << args.blowup_log, "field": "p=3*2^30+1", "parallelism": par,
                        "transport": dist_report},
-            "oracle_verified": bool(verified),
+            "full": args.full,
+            "oracle_verified": bool(verified) if args.full else None,     # compared only with --full
             "hbm_bytes_per_rank_max": int(hbm_max),
             "roofline": roofline,
             "whole_commit": whole,
@@ -808,6 +835,39 @@ def main():
         dist.destroy_process_group()
     elif pg is not None:
         _team_wait(pg)                   # the ranks that waited for this team run
+
+
+DUMP_SAMPLE = 1 << 18     # elements kept of a resident layer longer than this
+
+
+def dump_outputs(out_dir, res, ctx, log_n):
+    """--dump-outputs: what the last timed step handed its caller, as
+    out_dir/<name>.npy.  The fri_commit_result `res`: roots.npy (n_layers x 32
+    digest bytes, float32), betas.npy (float64), final.npy (final value, final
+    degree, layers, rounds; float64), channel_digest.npy (32 bytes, float32).
+    With `ctx` (one GPU, one context) also the layers that commit left
+    resident, read back with fri_layer_copy: layer_KK.npy (float64, exact for
+    u32), whole when it has at most DUMP_SAMPLE elements, else the elements at
+    DUMP_SAMPLE indices drawn once from a generator seeded with the layer
+    number (the same indices in every run and every build).  About 16 MB at
+    2^24.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "roots": np.array([list(bytes(res.roots[k])) for k in range(res.n_layers)], dtype=np.float32).reshape(-1, 32),
+        "betas": np.array([int(res.betas[i]) for i in range(res.n_rounds)], dtype=np.float64),
+        "final": np.array([res.final_value, res.final_degree, res.n_layers, res.n_rounds], dtype=np.float64),
+        "channel_digest": np.array(list(bytes(res.channel_out.digest)), dtype=np.float32),
+    }
+    if ctx is not None:
+        for k in range(res.n_layers):
+            layer = ctx.layer(k, log_n)
+            if layer.size > DUMP_SAMPLE:
+                layer = layer[np.random.default_rng(k).integers(0, layer.size, DUMP_SAMPLE)]
+            arrays[f"layer_{k:02d}"] = layer.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def devices_used(team_devices, world, ndev, n_ranks):
@@ -876,7 +936,7 @@ def _team_stage(fri_amd, devices, points, args, timed):
     for name, L in points:
         dL = 1 << (L - args.blowup_log)
         cf = _coeffs(42, dL, fri_amd.P)
-        exp = _expected(L, args.blowup_log)
+        exp = _expected(L, args.blowup_log, args.full)
         first = ctx.commit(cf, L)          # host input: every rank stages it (ranks 1..G-1: their copies)
         if exp is not None and not _matches(first, exp):
             raise RuntimeError(f"team transcript of 2^{L} differs from the C oracle's")

@@ -88,3 +88,43 @@ def test_devices_used_reports_distinct_gpus(team, world, ndev, ranks, want):
     device mark the run oversubscribed (such a run is not an
     N-GPU scaling point)."""
     assert bench.devices_used(team, world, ndev, ranks) == want
+
+
+def test_dump_outputs_writes_the_result_and_a_fixed_layer_sample(tmp_path):
+    """--dump-outputs: the fri_commit_result as float arrays, short layers
+    whole, long ones at indices that depend on the layer number alone (two
+    runs, two builds: the same elements)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "stark-prover_amd", "python"))
+    import fri_amd
+
+    log_n = 20
+    res = fri_amd.CommitResult()
+    res.n_layers, res.n_rounds, res.log_n, res.final_value, res.final_degree = 3, 2, log_n, 0xC0000000, 0
+    for k in range(3):
+        res.roots[k][:] = bytes((7 * k + i) % 256 for i in range(32))
+    res.betas[0], res.betas[1] = 0xBFFFFFFF, 5
+    res.channel_out.digest[:] = bytes(range(32))
+
+    class Ctx:
+        def layer(self, k, ln):
+            assert ln == log_n
+            return ((np.arange(1 << (ln - k), dtype=np.uint64) * 2654435761 + k) % fri_amd.P).astype(np.uint32)
+
+    names = bench.dump_outputs(str(tmp_path / "a"), res, Ctx(), log_n)
+    assert names == ["betas", "channel_digest", "final", "layer_00", "layer_01", "layer_02", "roots"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) < 64 << 20
+    assert got["roots"].shape == (3, 32) and bytes(got["roots"][2].astype(np.uint8)) == bytes(res.roots[2])
+    assert got["betas"].tolist() == [0xBFFFFFFF, 5]                      # u32 values survive exactly
+    assert got["final"].tolist() == [0xC0000000, 0, 3, 2]
+    assert got["channel_digest"].tolist() == list(range(32))
+    assert got["layer_02"].size == bench.DUMP_SAMPLE and np.array_equal(got["layer_02"], Ctx().layer(2, log_n))
+    assert got["layer_00"].size == bench.DUMP_SAMPLE                    # 2^20 elements: sampled
+    idx = np.random.default_rng(0).integers(0, 1 << log_n, bench.DUMP_SAMPLE)
+    assert np.array_equal(got["layer_00"], Ctx().layer(0, log_n)[idx])
+    # without a context (N > 1): the result alone; a second run writes the same bytes
+    assert bench.dump_outputs(str(tmp_path / "b"), res, None, log_n) == ["betas", "channel_digest", "final", "roots"]
+    bench.dump_outputs(str(tmp_path / "c"), res, Ctx(), log_n)
+    assert all((tmp_path / "a" / f"{n}.npy").read_bytes() == (tmp_path / "c" / f"{n}.npy").read_bytes() for n in names)

@@ -11,12 +11,12 @@ TAG=${1:-rNN}
 R=$PWD
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
-timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err
-timeout -k 10 200 python3 bench.py --log-n 20 --steps 50 --no-cpu-baseline --no-extras > $O/bench_2p20.json 2>> $O/bench.err
-timeout -k 10 300 python3 bench.py --log-n 28 --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_2p28.json 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err
+timeout -k 10 200 python3 bench.py --full --log-n 20 --steps 50 --no-cpu-baseline --no-extras > $O/bench_2p20.json 2>> $O/bench.err
+timeout -k 10 300 python3 bench.py --full --log-n 28 --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_2p28.json 2>> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- \
-    python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/rocprof.err
+    python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/rocprof.err
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- \
     python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-extras > /dev/null 2>> $O/rocprof.err
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- \

@@ -48,9 +48,9 @@ collect)
     ;;
 proj)
     LS=${*:-28 24}
-    timeout -k 10 300 python3 bench.py --log-n 28 --steps 5 --warmup 2 --no-cpu-baseline --no-extras \
+    timeout -k 10 300 python3 bench.py --full --log-n 28 --steps 5 --warmup 2 --no-cpu-baseline --no-extras \
         > $O/${TAG}_proj_bench28.json
-    timeout -k 10 200 python3 bench.py --steps 20 --no-cpu-baseline --no-extras > $O/${TAG}_proj_bench24.json
+    timeout -k 10 200 python3 bench.py --full --steps 20 --no-cpu-baseline --no-extras > $O/${TAG}_proj_bench24.json
     for W in 8 4 2; do for L in $LS; do
         timeout -k 10 300 python3 tools/shard_projection.py --log-n $L --world $W --rank 0 --steps 5 \
             > $O/${TAG}_proj_wall_${L}_w$W.txt 2>&1
