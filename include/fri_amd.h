@@ -136,6 +136,65 @@ int fri_interpolate_points(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys,
 int fri_evaluate(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs,
                  size_t count, uint32_t* out);
 
+/* ------------------------------------------------- polynomial arithmetic */
+/* Polynomial<M>::mul_assign, div_rem and compose (src/polynomial/ops.rs) on
+ * the device.  Operands are host arrays of canonical coefficients
+ * (coefficient j = x^j; a value >= p gives FRI_EINVAL) and may carry
+ * trailing zeros: they are trimmed first, as Polynomial::new does
+ * (ops.rs:19-37).  Every length written back is a trimmed length, 0 for the
+ * zero polynomial.  An output capacity that is too small gives FRI_EINVAL
+ * with the needed length in the length output.  Field arithmetic is exact
+ * and quotient and remainder are unique, so the coefficients equal the
+ * reference's whatever algorithm computes them.  On a multi-GPU context the
+ * calls run on rank 0. */
+#define FRI_POLY_FORCE_NTT    1u   /* test/measurement hook: never take the direct kernel */
+#define FRI_POLY_FORCE_DIRECT 2u   /* test/measurement hook: take it (FRI_EINVAL if the
+                                      short operand exceeds FRI_POLY_DIRECT_LIMIT) */
+/* The direct convolution kernel stages the short operand in LDS: its hard
+ * limit, in coefficients of the shorter operand. */
+#define FRI_POLY_DIRECT_LIMIT 4096
+/* fri_poly_mul takes the direct kernel when min(la, lb) <= this: the
+ * measured crossover (profiles/poly_arith.txt, table (i)) — the largest
+ * short length, rounded down to a power of two, at which the direct kernel
+ * is not slower than the NTT path against a long operand of 2^16
+ * coefficients (0.10 ms against 0.12 ms at 1024; 0.14 against 0.12 at 2048;
+ * the same in three runs). */
+#define FRI_POLY_DIRECT_MAX   1024
+
+/* a * b — Polynomial::mul_assign (ops.rs:114-138, schoolbook O(la*lb)).
+ * A zero operand gives *len_out = 0 (ops.rs:115-121); otherwise the product
+ * has la + lb - 1 coefficients (trimmed lengths) and needs
+ * next_pow2(la + lb - 1) <= 2^log_n_max.  Two forward NTTs of that size, a
+ * pointwise product and one inverse NTT; with min(la, lb) <=
+ * FRI_POLY_DIRECT_MAX one direct convolution kernel, O(la*lb), instead.
+ * flags: 0 or one FRI_POLY_FORCE_*. */
+int fri_poly_mul(fri_ctx* ctx, const uint32_t* a, size_t la, const uint32_t* b, size_t lb,
+                 uint32_t flags, uint32_t* out, size_t out_cap, size_t* len_out);
+
+/* (q, r) with a = q*b + r, deg r < deg b — Polynomial::div_rem
+ * (ops.rs:141-191, long division with one Fermat inverse per quotient
+ * step).  b zero: FRI_EINVAL, "Division by zero polynomial" (ops.rs:143).
+ * deg a < deg b: q = 0 and r = a (ops.rs:145-147).  Otherwise q has
+ * la - lb + 1 coefficients and q_cap >= la - lb + 1, r_cap >= lb - 1 are
+ * required (*r_len is then the trimmed length, <= lb - 1).  Newton inversion
+ * of the reversed divisor, O(n log n): accepted sizes (trimmed) are exactly
+ *   la <= 2^log_n_max  and  next_pow2(la - lb + 1) <= 2^(log_n_max - 1),
+ * which holds for every la <= 2^(log_n_max - 2) and every la <= 2^(log_n_max
+ * - 1) + lb - 1. */
+int fri_poly_div_rem(fri_ctx* ctx, const uint32_t* a, size_t la, const uint32_t* b, size_t lb,
+                     uint32_t* q_out, size_t q_cap, size_t* q_len,
+                     uint32_t* r_out, size_t r_cap, size_t* r_len);
+
+/* p(q(x)) — Polynomial::compose (ops.rs:214-237, Horner over polynomials).
+ * p zero gives zero; q zero or a constant c gives the constant p(c), which
+ * may trim to zero (ops.rs:993-1019); otherwise the result has
+ * deg p * deg q + 1 coefficients and needs N = next_pow2(deg p * deg q + 1)
+ * <= 2^log_n_max.  One NTT of q, Horner of p at those N values, one inverse
+ * NTT: the cost is O(lp * N) field products, so this is for compositions
+ * with a short p or a low-degree q (f(g*x): N = next_pow2(lp)). */
+int fri_poly_compose(fri_ctx* ctx, const uint32_t* p, size_t lp, const uint32_t* q, size_t lq,
+                     uint32_t* out, size_t out_cap, size_t* len_out);
+
 /* ---------------------------------------------------------------- FRI ops */
 /* One FRI fold of a layer of size m = 2^log_m living on the coset
  * layer_offset * <w_m> (natural order): out[i] = P'(x_i^2), i < m/2, with

@@ -141,7 +141,7 @@ extern "C" int fri_ctx_destroy(fri_ctx* ctx) {
 }
 
 extern "C" const char* fri_last_error(const fri_ctx* ctx) { return ctx ? ctx->err.c_str() : "no context"; }
-extern "C" const char* fri_version(void) { return "fri_amd 0.1 (gfx950, p=3*2^30+1)"; }
+extern "C" const char* fri_version(void) { return "fri_amd 0.2 (gfx950, p=3*2^30+1)"; }
 // Diagnostic: per-layer top-kernel phase stamps of the last commit
 // (100 MHz ticks), only in the -DFRI_STAMPS build.
 extern "C" int fri_debug_stamps(fri_ctx* ctx, uint64_t* out, size_t cap) {

@@ -3,6 +3,7 @@
 //   fri_ctx.hip        context lifetime, profiling spans, diagnostics
 //   fri_ops.hip        kernel-level entry points: batch inverse, LDE,
 //                      interpolation, evaluation, fold, Merkle root
+//   fri_poly.hip       polynomial arithmetic: mul, div_rem, compose
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
@@ -384,6 +385,31 @@ inline NttPlan lde_plan(fri_ctx* ctx, uint32_t log_n) {
     p.log_n = log_n;
     p.tw = ctx->tw_fwd;
     return p;
+}
+
+// Device scratch of at least `words` words for the interpolation / evaluation
+// partials (grown on demand, freed with the context).
+inline int ensure_tmp(fri_ctx* ctx, size_t words) {
+    if (words <= ctx->interp_cap) return FRI_OK;
+    FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->interp_tmp) dfree(ctx, ctx->interp_tmp);
+    ctx->interp_tmp = nullptr;
+    ctx->interp_cap = 0;
+    if (dalloc(ctx, &ctx->interp_tmp, words * 4) != hipSuccess) return fail(ctx, FRI_ENOMEM, "partials scratch");
+    ctx->interp_cap = words;
+    return FRI_OK;
+}
+// Scratch grown past TMP_KEEP_WORDS is released after the call that grew it,
+// so one large fri_merkle_root (the tree of 2^28 values is 16 GiB) does not
+// pin HBM for the life of the context and starve a later commit plan; smaller
+// scratch is kept (no hipFree, which synchronises the device, per call).
+constexpr size_t TMP_KEEP_WORDS = (size_t)1 << 26;   // 256 MiB
+inline void tmp_trim(fri_ctx* ctx) {
+    if (ctx->interp_cap <= TMP_KEEP_WORDS) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    dfree(ctx, ctx->interp_tmp);
+    ctx->interp_tmp = nullptr;
+    ctx->interp_cap = 0;
 }
 
 inline void digest_to_bytes(const uint32_t* w, uint8_t* out) {

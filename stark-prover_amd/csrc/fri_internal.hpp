@@ -88,6 +88,21 @@ void launch_interp_eval(const uint32_t* xs, const uint32_t* c, size_t n, uint32_
 size_t evaluate_tmp_words(size_t d, size_t count);
 void launch_evaluate(const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count, uint32_t* out,
                      uint32_t* tmp, hipStream_t s);
+// Polynomial arithmetic (fri_poly.hip).  Pointwise on two transforms of n
+// canonical values: out = a*b*R^-1, and the Newton step out = g*(2 - f*g)*R^-2
+// (the caller's inverse transform scales by R or R^2, and N^-1); out may
+// alias an operand.
+void launch_poly_pointwise_mul(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, hipStream_t s);
+void launch_poly_newton(const uint32_t* f, const uint32_t* g, uint32_t* out, size_t n, hipStream_t s);
+// out[i] = sum_j sht[j]*lng[i - j], i < n_out, canonical; ls <= POLY_DIRECT_LIMIT
+// (the short operand and the long operand's window are staged in LDS).
+constexpr size_t POLY_DIRECT_LIMIT = 4096;   // == FRI_POLY_DIRECT_LIMIT
+void launch_poly_conv_direct(const uint32_t* lng, size_t ll, const uint32_t* sht, size_t ls, uint32_t* out,
+                             size_t n_out, hipStream_t s);
+// dst[i] = src[top - i] for i < cnt (cnt <= top + 1), 0 for cnt <= i < n.
+void launch_poly_reverse(const uint32_t* src, size_t top, size_t cnt, uint32_t* dst, size_t n, hipStream_t s);
+// r[i] = a[i] - t[i], i < n.
+void launch_poly_sub(const uint32_t* a, const uint32_t* t, uint32_t* r, size_t n, hipStream_t s);
 struct DecommitPlan {
     uint64_t index;
     uint32_t log_n, n_layers;

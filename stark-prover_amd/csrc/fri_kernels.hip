@@ -1225,4 +1225,123 @@ void launch_decommit_gather(const uint32_t* layers, const uint32_t* trees, const
     hipLaunchKernelGGL(k_decommit_gather, dim3(dp.n_layers), dim3(64), 0, s, layers, trees, top, dp, out);
 }
 
+// ================================================= polynomial arithmetic ==
+// fri_poly_mul / fri_poly_div_rem (fri_poly.hip; ops.rs:114-191).
+//
+// Pointwise kernels on NTT outputs.  The transforms leave canonical values,
+// so every mmul of two of them carries one R^-1: the product kernel leaves
+// A*B*R^-1, the Newton kernel G*(2 - F*G)*R^-2 (2*R^-1 - F*G*R^-1 is
+// (2 - F*G)*R^-1).  The caller folds R (R^2) and N^-1 into the inverse
+// transform's post-scale table, so there is no conversion pass.  16-byte
+// loads and stores when the three pointers are aligned; out may alias a or b
+// (each element is read, then written, by the same lane).
+template <bool NEWTON>
+__device__ __forceinline__ uint32_t poly_pw(uint32_t a, uint32_t b, uint32_t two_rinv) {
+    const uint32_t t = mmul(a, b);
+    return NEWTON ? mmul(b, sub(two_rinv, t)) : t;
+}
+template <bool NEWTON>
+__global__ __launch_bounds__(256) void k_poly_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n,
+                                                        size_t n4, uint32_t two_rinv) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint4* a4 = reinterpret_cast<const uint4*>(a);
+    const uint4* b4 = reinterpret_cast<const uint4*>(b);
+    uint4* o4 = reinterpret_cast<uint4*>(out);
+    for (size_t i = t0; i < n4; i += stride) {
+        const uint4 x = a4[i], y = b4[i];
+        uint4 r;
+        r.x = poly_pw<NEWTON>(x.x, y.x, two_rinv);
+        r.y = poly_pw<NEWTON>(x.y, y.y, two_rinv);
+        r.z = poly_pw<NEWTON>(x.z, y.z, two_rinv);
+        r.w = poly_pw<NEWTON>(x.w, y.w, two_rinv);
+        o4[i] = r;
+    }
+    for (size_t i = 4 * n4 + t0; i < n; i += stride) out[i] = poly_pw<NEWTON>(a[i], b[i], two_rinv);
+}
+template <bool NEWTON>
+static void launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, hipStream_t s) {
+    if (!n) return;
+    const bool vec = ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & 15u) == 0;
+    const size_t n4 = vec ? n / 4 : 0;
+    const size_t work = n4 ? n4 : n;
+    size_t blocks = (work + 255) / 256;
+    if (blocks > 8192) blocks = 8192;                              // grid-stride beyond 2^21 lanes
+    const uint32_t rinv = from_mont(1u);
+    hipLaunchKernelGGL((k_poly_pointwise<NEWTON>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, out, n, n4,
+                       add(rinv, rinv));
+}
+void launch_poly_pointwise_mul(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n, hipStream_t s) {
+    launch_pointwise<false>(a, b, out, n, s);
+}
+void launch_poly_newton(const uint32_t* f, const uint32_t* g, uint32_t* out, size_t n, hipStream_t s) {
+    launch_pointwise<true>(f, g, out, n, s);
+}
+
+// Direct convolution with a short operand (`* (x - c)`, the products of a
+// small composition): out[i] = sum_j sht[j] * lng[i - j] for i < n_out, one
+// lane per output coefficient, no transform.  The short operand is staged in
+// LDS in Montgomery form (so each product comes out canonical), next to the
+// window of the long operand the workgroup's 256 outputs read, zero-filled
+// outside [0, ll): the inner loop has no bounds test, the short operand is an
+// LDS broadcast and the window is read at consecutive addresses across lanes.
+// Terms are canonical (< 2^32), at most POLY_DIRECT_LIMIT = 2^12 of them, so
+// a 64-bit sum stays below 2^44 and is reduced once (two REDCs).
+__global__ __launch_bounds__(256) void k_poly_conv_direct(const uint32_t* __restrict__ lng, size_t ll,
+                                                          const uint32_t* __restrict__ sht, uint32_t ls,
+                                                          uint32_t* __restrict__ out, size_t n_out) {
+    extern __shared__ uint32_t poly_sm[];
+    uint32_t* sh = poly_sm;                 // ls words
+    uint32_t* win = poly_sm + ls;           // 256 + ls - 1 words: lng[i0 - (ls - 1) .. i0 + 255]
+    const size_t i0 = (size_t)blockIdx.x * 256;
+    for (uint32_t j = threadIdx.x; j < ls; j += 256) sh[j] = to_mont(sht[j]);
+    const uint32_t wn = 256 + ls - 1;
+    for (uint32_t t = threadIdx.x; t < wn; t += 256) {
+        const size_t pos = i0 + t;          // index + (ls - 1)
+        win[t] = (pos >= ls - 1 && pos - (ls - 1) < ll) ? lng[pos - (ls - 1)] : 0u;
+    }
+    __syncthreads();
+    const size_t i = i0 + threadIdx.x;
+    if (i >= n_out) return;
+    const uint32_t* w = win + threadIdx.x + (ls - 1);   // w[-j] = lng[i - j]
+    uint64_t acc = 0;
+#pragma unroll 4
+    for (uint32_t j = 0; j < ls; j++) acc += mmul(w[-(int)j], sh[j]);
+    out[i] = mmul(redc(acc), R2_MOD_P);
+}
+void launch_poly_conv_direct(const uint32_t* lng, size_t ll, const uint32_t* sht, size_t ls, uint32_t* out,
+                             size_t n_out, hipStream_t s) {
+    if (!n_out || !ls || ls > POLY_DIRECT_LIMIT) return;
+    const size_t lds = (2 * ls + 255) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_poly_conv_direct, dim3((unsigned)((n_out + 255) / 256)), dim3(256), lds, s, lng, ll, sht,
+                       (uint32_t)ls, out, n_out);
+}
+
+// Division helpers.  Reverse-truncate-pad: dst[i] = src[top - i] for
+// i < cnt (cnt <= top + 1), 0 for cnt <= i < n.  Remainder: r = a - t on the
+// low n coefficients.
+__global__ __launch_bounds__(256) void k_poly_reverse(const uint32_t* __restrict__ src, size_t top, size_t cnt,
+                                                      uint32_t* __restrict__ dst, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        dst[i] = i < cnt ? src[top - i] : 0u;
+}
+__global__ __launch_bounds__(256) void k_poly_sub(const uint32_t* __restrict__ a, const uint32_t* __restrict__ t,
+                                                  uint32_t* __restrict__ r, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) r[i] = sub(a[i], t[i]);
+}
+static unsigned poly_blocks(size_t n) {
+    const size_t b = (n + 255) / 256;
+    return (unsigned)(b > 8192 ? 8192 : b);
+}
+void launch_poly_reverse(const uint32_t* src, size_t top, size_t cnt, uint32_t* dst, size_t n, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_poly_reverse, dim3(poly_blocks(n)), dim3(256), 0, s, src, top, cnt, dst, n);
+}
+void launch_poly_sub(const uint32_t* a, const uint32_t* t, uint32_t* r, size_t n, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_poly_sub, dim3(poly_blocks(n)), dim3(256), 0, s, a, t, r, n);
+}
+
 }  // namespace fri

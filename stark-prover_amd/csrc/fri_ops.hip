@@ -72,31 +72,6 @@ extern "C" int fri_interpolate(fri_ctx* ctx, const uint32_t* ys, uint32_t log_n,
     return FRI_OK;
 }
 
-// Device scratch of at least `words` words for the interpolation / evaluation
-// partials (grown on demand, freed with the context).
-static int ensure_tmp(fri_ctx* ctx, size_t words) {
-    if (words <= ctx->interp_cap) return FRI_OK;
-    FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->interp_tmp) dfree(ctx, ctx->interp_tmp);
-    ctx->interp_tmp = nullptr;
-    ctx->interp_cap = 0;
-    if (dalloc(ctx, &ctx->interp_tmp, words * 4) != hipSuccess) return fail(ctx, FRI_ENOMEM, "partials scratch");
-    ctx->interp_cap = words;
-    return FRI_OK;
-}
-// Scratch grown past TMP_KEEP_WORDS is released after the call that grew it,
-// so one large fri_merkle_root (the tree of 2^28 values is 16 GiB) does not
-// pin HBM for the life of the context and starve a later commit plan; smaller
-// scratch is kept (no hipFree, which synchronises the device, per call).
-constexpr size_t TMP_KEEP_WORDS = (size_t)1 << 26;   // 256 MiB
-static void tmp_trim(fri_ctx* ctx) {
-    if (ctx->interp_cap <= TMP_KEEP_WORDS) return;
-    (void)hipStreamSynchronize(ctx->stream);
-    dfree(ctx, ctx->interp_tmp);
-    ctx->interp_tmp = nullptr;
-    ctx->interp_cap = 0;
-}
-
 // interpolate_lagrange_polynomials (interpolation.rs:121-152) on arbitrary
 // points: weights, c_j = y_j w_j, f on the 2^k-th roots of unity, iNTT
 // (fri_kernels.hip "arbitrary-point interpolate").

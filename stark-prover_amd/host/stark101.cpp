@@ -790,6 +790,60 @@ Poly interpolate(const std::vector<FE>& xs, const std::vector<FE>& ys) {
     return Poly(to_fe(c.data(), len));
 }
 
+// ---- Poly arithmetic on the device (ops.rs:114-237) ------------------------
+namespace {
+std::vector<uint32_t> trimmed_u32(const std::vector<FE>& v) {
+    size_t n = v.size();
+    while (n > 0 && v[n - 1] == FE::zero()) n--;
+    std::vector<uint32_t> o(n);
+    for (size_t i = 0; i < n; i++) o[i] = static_cast<uint32_t>(v[i].value());
+    return o;
+}
+}  // namespace
+
+template <>
+void Polynomial<P>::mul_assign(const Polynomial<P>& rhs) {
+    const auto a = trimmed_u32(coefficients), b = trimmed_u32(rhs.coefficients);
+    if (a.empty() || b.empty()) {                               // ops.rs:115-121
+        *this = Poly();
+        return;
+    }
+    auto gpu = Gpu::thread_default(ceil_log2(a.size() + b.size() - 1));
+    std::vector<uint32_t> out(a.size() + b.size() - 1);
+    size_t len = 0;
+    gpu->check(fri_poly_mul(gpu->ctx(), a.data(), a.size(), b.data(), b.size(), 0, out.data(), out.size(), &len),
+               "fri_poly_mul");
+    *this = Poly(to_fe(out.data(), len));
+}
+
+template <>
+std::pair<Poly, Poly> Polynomial<P>::div_rem(const Polynomial<P>& rhs) const {
+    const auto a = trimmed_u32(coefficients), b = trimmed_u32(rhs.coefficients);
+    if (b.empty()) throw Panic("Division by zero polynomial");  // ops.rs:143
+    if (a.size() < b.size()) return {Poly(), Poly(to_fe(a.data(), a.size()))};   // ops.rs:145-147
+    auto gpu = Gpu::thread_default(ceil_log2(a.size()) + 2);    // every la <= 2^(log_n_max - 2) is accepted
+    std::vector<uint32_t> q(a.size() - b.size() + 1), r(b.size());
+    size_t lq = 0, lr = 0;
+    gpu->check(fri_poly_div_rem(gpu->ctx(), a.data(), a.size(), b.data(), b.size(), q.data(), q.size(), &lq, r.data(),
+                                r.size(), &lr),
+               "fri_poly_div_rem");
+    return {Poly(to_fe(q.data(), lq)), Poly(to_fe(r.data(), lr))};
+}
+
+template <>
+Poly Polynomial<P>::compose(const Polynomial<P>& other) const {
+    const auto p = trimmed_u32(coefficients), q = trimmed_u32(other.coefficients);
+    if (p.empty()) return Poly();
+    const size_t n = q.size() <= 1 ? 1 : (p.size() - 1) * (q.size() - 1) + 1;
+    const uint32_t log_n = ceil_log2(n > p.size() ? n : p.size());
+    auto gpu = Gpu::thread_default(log_n);
+    std::vector<uint32_t> out(n);
+    size_t len = 0;
+    gpu->check(fri_poly_compose(gpu->ctx(), p.data(), p.size(), q.data(), q.size(), out.data(), out.size(), &len),
+               "fri_poly_compose");
+    return Poly(to_fe(out.data(), len));
+}
+
 std::vector<FE> batch_inverse(const std::vector<FE>& xs) {
     if (xs.empty()) return {};
     auto gpu = Gpu::thread_default(ceil_log2(xs.size()));

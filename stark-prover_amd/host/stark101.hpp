@@ -6,7 +6,9 @@
 // the reference's names, argument meaning and panic behaviour:
 //
 //   FieldElement<M>   src/fields/element.rs:7-147   (host scalar arithmetic)
-//   Polynomial<M>     src/polynomial/ops.rs:10-83   (new/trim, degree, Horner)
+//   Polynomial<M>     src/polynomial/ops.rs:10-342  (new/trim, degree, Horner,
+//                                                    add/sub/mul/div_rem/compose,
+//                                                    scalar_mul/div, operators)
 //   CosetFri<M>       src/fri/coset_fri.rs:9-36
 //   Channel<M>        src/channel/channel.rs:14-96  (authoritative transcript)
 //   MerkleTree        src/merkle/mod.rs:5-27        (built on the GPU)
@@ -27,6 +29,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "fri_amd.h"
@@ -123,8 +126,22 @@ FieldElement<M> FieldElement<M>::random() {
 }
 
 // ---------------------------------------------------------------- Polynomial
-// ops.rs:10-83: coefficients[i] multiplies x^i, trailing zeros trimmed,
+// ops.rs:10-342: coefficients[i] multiplies x^i, trailing zeros trimmed,
 // degree = len - 1 or -1 for the zero polynomial.
+//
+// Arithmetic.  add/sub/scalar_* are O(n) host loops for every modulus.
+// mul_assign, div_rem and compose are the reference's schoolbook algorithms
+// on the host for a general modulus (the reference's own unit tests use 7, 17
+// and 23; the device has one field); for the frozen field (Poly, below) they
+// are explicit specialisations that always run on the device
+// (fri_poly_mul / fri_poly_div_rem / fri_poly_compose through
+// Gpu::thread_default): no size switch, no CPU fallback.
+//
+// Deviation: scalar_mul, like the reference's (ops.rs:194-198), does not
+// re-trim, so scalar_mul(0) leaves zeros under a stale degree.  Every
+// operation here treats such an all-zero polynomial as the zero polynomial
+// (it looks at the coefficients, not at `degree`); the reference's div_rem
+// would loop forever on such a divisor.
 template <uint64_t MODULUS>
 class Polynomial {
   public:
@@ -149,12 +166,101 @@ class Polynomial {
     friend bool operator==(const Polynomial& a, const Polynomial& b) { return a.coefficients == b.coefficients; }
     friend bool operator!=(const Polynomial& a, const Polynomial& b) { return !(a == b); }
 
+    void add_assign(const Polynomial& rhs) {                     // ops.rs:87-98
+        if (rhs.trimmed_len() == 0) return;
+        if (coefficients.size() < rhs.coefficients.size()) coefficients.resize(rhs.coefficients.size());
+        for (size_t i = 0; i < rhs.coefficients.size(); i++) coefficients[i] += rhs.coefficients[i];
+        update_degree();
+    }
+    void sub_assign(const Polynomial& rhs) {                     // ops.rs:101-112
+        if (rhs.trimmed_len() == 0) return;
+        if (coefficients.size() < rhs.coefficients.size()) coefficients.resize(rhs.coefficients.size());
+        for (size_t i = 0; i < rhs.coefficients.size(); i++) coefficients[i] -= rhs.coefficients[i];
+        update_degree();
+    }
+    void mul_assign(const Polynomial& rhs);                      // ops.rs:114-138
+    // (quotient, remainder), ops.rs:141-191; Panic("Division by zero polynomial")
+    std::pair<Polynomial, Polynomial> div_rem(const Polynomial& rhs) const;
+    void scalar_mul(FE s) {                                      // ops.rs:194-198: degree kept
+        for (auto& c : coefficients) c *= s;
+    }
+    void scalar_div(FE s) {                                      // ops.rs:201-210
+        if (s == FE::zero()) throw Panic("Division by zero in a finite field is not allowed.");
+        const FE inv = s.inverse();
+        for (auto& c : coefficients) c *= inv;
+    }
+    Polynomial compose(const Polynomial& other) const;           // self(other), ops.rs:214-237
+
+    // ops.rs:246-342, plus / and % over div_rem
+    friend Polynomial operator+(Polynomial a, const Polynomial& b) { a.add_assign(b); return a; }
+    friend Polynomial operator-(Polynomial a, const Polynomial& b) { a.sub_assign(b); return a; }
+    friend Polynomial operator*(Polynomial a, const Polynomial& b) { a.mul_assign(b); return a; }
+    friend Polynomial operator/(const Polynomial& a, const Polynomial& b) { return a.div_rem(b).first; }
+    friend Polynomial operator%(const Polynomial& a, const Polynomial& b) { return a.div_rem(b).second; }
+    Polynomial& operator+=(const Polynomial& b) { add_assign(b); return *this; }
+    Polynomial& operator-=(const Polynomial& b) { sub_assign(b); return *this; }
+    Polynomial& operator*=(const Polynomial& b) { mul_assign(b); return *this; }
+
   private:
+    size_t trimmed_len() const {                                 // the coefficients decide, not a stale degree
+        size_t n = coefficients.size();
+        while (n > 0 && coefficients[n - 1] == FE::zero()) n--;
+        return n;
+    }
     void update_degree() {
         while (!coefficients.empty() && coefficients.back() == FE::zero()) coefficients.pop_back();
         degree = coefficients.empty() ? -1 : static_cast<int64_t>(coefficients.size()) - 1;
     }
 };
+
+// The reference's schoolbook algorithms (any modulus but the frozen one).
+template <uint64_t M>
+void Polynomial<M>::mul_assign(const Polynomial& rhs) {
+    const size_t la = trimmed_len(), lb = rhs.trimmed_len();
+    if (la == 0 || lb == 0) {                                    // ops.rs:115-121
+        *this = Polynomial();
+        return;
+    }
+    std::vector<FE> prod(la + lb - 1);
+    for (size_t i = 0; i < la; i++) {
+        if (coefficients[i] == FE::zero()) continue;
+        for (size_t j = 0; j < lb; j++) prod[i + j] += coefficients[i] * rhs.coefficients[j];
+    }
+    coefficients = std::move(prod);
+    update_degree();
+}
+
+template <uint64_t M>
+std::pair<Polynomial<M>, Polynomial<M>> Polynomial<M>::div_rem(const Polynomial& rhs) const {
+    const size_t la = trimmed_len(), lb = rhs.trimmed_len();
+    if (lb == 0) throw Panic("Division by zero polynomial");     // ops.rs:143
+    std::vector<FE> rem(coefficients.begin(), coefficients.begin() + static_cast<std::ptrdiff_t>(la));
+    if (la < lb) return {Polynomial(), Polynomial(std::move(rem))};   // ops.rs:145-147
+    std::vector<FE> quot(la - lb + 1);
+    const FE lead_inv = rhs.coefficients[lb - 1].inverse();
+    while (rem.size() >= lb) {                                   // one quotient step per remaining top term
+        const size_t shift = rem.size() - lb;
+        const FE ratio = rem.back() * lead_inv;
+        quot[shift] += ratio;
+        for (size_t i = 0; i < lb; i++) rem[i + shift] -= ratio * rhs.coefficients[i];
+        while (!rem.empty() && rem.back() == FE::zero()) rem.pop_back();
+    }
+    return {Polynomial(std::move(quot)), Polynomial(std::move(rem))};
+}
+
+template <uint64_t M>
+Polynomial<M> Polynomial<M>::compose(const Polynomial& other) const {
+    Polynomial result;                                           // Horner over polynomials, highest power first
+    for (size_t i = trimmed_len(); i-- > 0;) {
+        if (result.is_zero()) {
+            result = Polynomial(std::vector<FE>{coefficients[i]});
+        } else {
+            result.mul_assign(other);
+            result.add_assign(Polynomial(std::vector<FE>{coefficients[i]}));
+        }
+    }
+    return result;
+}
 
 // ------------------------------------------------------------------ CosetFri
 // coset_fri.rs:9-36: D = { offset * omega^i : i < domain_size }.
@@ -245,6 +351,15 @@ using FE = FieldElement<P>;
 using Poly = Polynomial<P>;
 using FriChannel = Channel<P>;
 using Coset = CosetFri<P>;
+
+// Poly's products, divisions and compositions run on the device, always
+// (stark101.cpp; the context is Gpu::thread_default of the size they need).
+template <>
+void Polynomial<P>::mul_assign(const Polynomial<P>& rhs);
+template <>
+std::pair<Polynomial<P>, Polynomial<P>> Polynomial<P>::div_rem(const Polynomial<P>& rhs) const;
+template <>
+Polynomial<P> Polynomial<P>::compose(const Polynomial<P>& other) const;
 
 // omega_n = g^((p-1)/n) (frozen spec), n a power of two <= 2^30.
 FE omega(uint32_t log_n);

@@ -11,6 +11,9 @@ meaning, error behaviour):
 * ``lde`` / ``interpolate`` / ``evaluate`` / ``batch_inverse`` / ``fold`` — the
   polynomial / field kernels (src/polynomial/ops.rs, interpolation.rs,
   src/fields/element.rs, src/fri/fri_commit.rs:53-65).
+* ``poly_mul`` / ``poly_div_rem`` / ``poly_compose`` — Polynomial::mul_assign,
+  div_rem and compose (src/polynomial/ops.rs:114-237) on the device;
+  ``poly_add`` / ``poly_sub`` / ``poly_scalar_mul`` — the O(n) ones on the host.
 
 Every compute call goes through the HIP library; there is no CPU fallback.
 If the library or a gfx950 GPU is missing the calls raise ``FriError``.
@@ -40,6 +43,10 @@ FLAG_NO_GRAPH = 2
 FLAG_RANK_INPUTS = 4      # FRI_FLAG_RANK_INPUTS (fri_amd.h): team commit from the ranks' resident inputs
 MAX_INFLIGHT = 4          # FRI_MAX_INFLIGHT (fri_amd.h): pipelined commits pending per context
 DEFAULT_LANES = 3         # FRI_DEFAULT_LANES (fri_amd.h): commit lanes of a context
+POLY_FORCE_NTT = 1        # FRI_POLY_FORCE_* (fri_amd.h): fri_poly_mul's test/measurement hooks
+POLY_FORCE_DIRECT = 2
+POLY_DIRECT_LIMIT = 4096  # FRI_POLY_DIRECT_LIMIT: the direct kernel's hard limit (short operand)
+POLY_DIRECT_MAX = 1024    # FRI_POLY_DIRECT_MAX: fri_poly_mul's measured crossover to the direct kernel
 
 
 class FriError(RuntimeError):
@@ -107,6 +114,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_interpolate": (i32, [vp, pu32, u32, u32, pu32, ctypes.POINTER(sz)]),
         "fri_interpolate_points": (i32, [vp, pu32, pu32, sz, pu32, ctypes.POINTER(sz)]),
         "fri_evaluate": (i32, [vp, pu32, sz, pu32, sz, pu32]),
+        "fri_poly_mul": (i32, [vp, pu32, sz, pu32, sz, u32, pu32, sz, ctypes.POINTER(sz)]),
+        "fri_poly_div_rem": (i32, [vp, pu32, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz), pu32, sz,
+                                   ctypes.POINTER(sz)]),
+        "fri_poly_compose": (i32, [vp, pu32, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz)]),
         "fri_fold": (i32, [vp, pu32, u32, u32, u32, pu32]),
         "fri_merkle_root": (i32, [vp, pu32, sz, ctypes.c_char_p]),
         "fri_commit": (i32, [vp, pu32, sz, u32, u32, ctypes.POINTER(ChannelState), u32, pu32,
@@ -327,6 +338,40 @@ class Context:
         out = np.empty(x.size, dtype=np.uint32)
         self._check(self.lib.fri_evaluate(self.h, _ptr(c), c.size, _ptr(x), x.size, _ptr(out)))
         return out
+
+    def poly_mul(self, a, b, force: Optional[str] = None) -> np.ndarray:
+        """a * b (Polynomial::mul_assign, ops.rs:114-138; fri_poly_mul), trimmed.
+        force: None, "ntt" or "direct" (the FRI_POLY_FORCE_* hooks)."""
+        flags = {None: 0, "ntt": POLY_FORCE_NTT, "direct": POLY_FORCE_DIRECT}[force]
+        x, y = _u32(a), _u32(b)
+        out = np.empty(max(1, x.size + y.size), dtype=np.uint32)
+        ln = ctypes.c_size_t()
+        self._check(self.lib.fri_poly_mul(self.h, _ptr(x), x.size, _ptr(y), y.size, flags, _ptr(out), out.size,
+                                          ctypes.byref(ln)))
+        return out[: ln.value]
+
+    def poly_div_rem(self, a, b):
+        """(q, r) with a = q*b + r, deg r < deg b (Polynomial::div_rem,
+        ops.rs:141-191; fri_poly_div_rem), both trimmed.  A zero divisor
+        raises FriError(FRI_EINVAL, "Division by zero polynomial")."""
+        x, y = _u32(a), _u32(b)
+        q = np.empty(max(1, x.size), dtype=np.uint32)
+        r = np.empty(max(1, x.size, y.size), dtype=np.uint32)
+        lq, lr = ctypes.c_size_t(), ctypes.c_size_t()
+        self._check(self.lib.fri_poly_div_rem(self.h, _ptr(x), x.size, _ptr(y), y.size, _ptr(q), q.size,
+                                              ctypes.byref(lq), _ptr(r), r.size, ctypes.byref(lr)))
+        return q[: lq.value], r[: lr.value]
+
+    def poly_compose(self, p, q) -> np.ndarray:
+        """p(q(x)) (Polynomial::compose, ops.rs:214-237; fri_poly_compose), trimmed."""
+        x, y = _u32(p), _u32(q)
+        lx = int(np.flatnonzero(x)[-1]) + 1 if x.any() else 0      # trimmed lengths size the output
+        ly = int(np.flatnonzero(y)[-1]) + 1 if y.any() else 0
+        out = np.empty(max(1, (lx - 1) * (ly - 1) + 1 if lx and ly > 1 else 1), dtype=np.uint32)
+        ln = ctypes.c_size_t()
+        self._check(self.lib.fri_poly_compose(self.h, _ptr(x), x.size, _ptr(y), y.size, _ptr(out), out.size,
+                                              ctypes.byref(ln)))
+        return out[: ln.value]
 
     def fold(self, layer, layer_offset: int, beta: int) -> np.ndarray:
         v = _u32(layer)
@@ -1147,6 +1192,60 @@ def _default_ctx(log_n: int) -> Context:
     c = Context.default(key)
     _CTX_CACHE[key] = c
     return c
+
+
+# ---- Polynomial arithmetic (src/polynomial/ops.rs) --------------------------
+def _trim(a: np.ndarray) -> np.ndarray:                                   # Polynomial::new (ops.rs:19-37)
+    nz = np.flatnonzero(a)
+    return a[: int(nz[-1]) + 1] if nz.size else a[:0]
+
+
+def _log_for(n: int) -> int:
+    return max(0, int(n - 1).bit_length())
+
+
+def poly_add(a, b) -> np.ndarray:
+    """a + b (Polynomial::add_assign, ops.rs:87-98), on the host, trimmed."""
+    x, y = _u32(a).astype(np.uint64), _u32(b).astype(np.uint64)
+    out = np.zeros(max(x.size, y.size), dtype=np.uint64)
+    out[: x.size] = x
+    out[: y.size] += y
+    return _trim((out % P).astype(np.uint32))
+
+
+def poly_sub(a, b) -> np.ndarray:
+    """a - b (Polynomial::sub_assign, ops.rs:101-112), on the host, trimmed."""
+    x, y = _u32(a).astype(np.uint64), _u32(b).astype(np.uint64)
+    out = np.zeros(max(x.size, y.size), dtype=np.uint64)
+    out[: x.size] = x
+    out[: y.size] += P - y
+    return _trim((out % P).astype(np.uint32))
+
+
+def poly_scalar_mul(a, s: int) -> np.ndarray:
+    """Polynomial::scalar_mul (ops.rs:194-198), on the host: like the reference
+    it does not re-trim (s = 0 leaves len(a) zeros)."""
+    if not 0 <= int(s) < P:
+        raise FriError(FRI_EINVAL, "field element not canonical (>= p)")
+    return ((_u32(a).astype(np.uint64) * np.uint64(int(s))) % np.uint64(P)).astype(np.uint32)
+
+
+def poly_mul(a, b, ctx: Optional[Context] = None, force: Optional[str] = None) -> np.ndarray:
+    """Polynomial::mul_assign (ops.rs:114-138) on the device."""
+    ctx = ctx or _default_ctx(_log_for(len(a) + len(b)))
+    return ctx.poly_mul(a, b, force=force)
+
+
+def poly_div_rem(a, b, ctx: Optional[Context] = None):
+    """Polynomial::div_rem (ops.rs:141-191) on the device: (q, r)."""
+    ctx = ctx or _default_ctx(_log_for(len(a)) + 2)
+    return ctx.poly_div_rem(a, b)
+
+
+def poly_compose(p, q, ctx: Optional[Context] = None) -> np.ndarray:
+    """Polynomial::compose (ops.rs:214-237) on the device: p(q(x))."""
+    ctx = ctx or _default_ctx(_log_for(max(1, len(p)) * max(1, len(q))))
+    return ctx.poly_compose(p, q)
 
 
 def fri_commit(coeffs: Sequence[int], log_n: int, channel: Channel, offset: int = GENERATOR,

@@ -1,0 +1,196 @@
+"""fri_poly_mul / fri_poly_div_rem / fri_poly_compose timings on the GPU
+(no device: the context creation fails and so does this tool).
+
+ (i)  the crossover behind FRI_POLY_DIRECT_MAX: fri_poly_mul under
+      FRI_POLY_FORCE_DIRECT and FRI_POLY_FORCE_NTT, alternating, short operand
+      1, 2, 4, ..., FRI_POLY_DIRECT_LIMIT against long operands of 2^10, 2^16
+      and 2^20 coefficients;
+ (ii) mul, div_rem and compose at a few sizes, beside the C oracle's
+      schoolbook (the reference's algorithm, one thread) where that takes
+      seconds, not minutes, and beside the sum of two fri_lde and one
+      fri_interpolate at the product's transform size (the same three
+      transforms through existing entry points).
+
+Every figure is the median of REPS synchronous C-ABI calls after WARM
+warm-ups, host clock around the call (uploads and read-back included).
+Shapes are seeded.  Usage: poly_arith_probe.py [--out FILE]"""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "stark-prover_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import fri_amd  # noqa: E402
+import fri_oracle as fo  # noqa: E402
+
+P = fri_amd.P
+WARM, REPS = 3, 11
+LOG_MAX = 22
+_lines = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    _lines.append(s)
+
+
+def coeffs(seed, n):
+    a = fo.splitmix64_np(seed, n)
+    if n and a[-1] == 0:
+        a[-1] = 1
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def median_ms(fn):
+    for _ in range(WARM):
+        fn()
+    ts = []
+    for _ in range(REPS):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * statistics.median(ts)
+
+
+def mul_call(ctx, a, b, flags):
+    out = np.empty(a.size + b.size, dtype=np.uint32)
+    ln = ctypes.c_size_t()
+    pa, pb, po = fri_amd._ptr(a), fri_amd._ptr(b), fri_amd._ptr(out)
+
+    def call():
+        rc = ctx.lib.fri_poly_mul(ctx.h, pa, a.size, pb, b.size, flags, po, out.size, ctypes.byref(ln))
+        assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+    return call
+
+
+def div_call(ctx, a, b):
+    q = np.empty(a.size, dtype=np.uint32)
+    r = np.empty(max(a.size, b.size), dtype=np.uint32)
+    lq, lr = ctypes.c_size_t(), ctypes.c_size_t()
+    pa, pb, pq, pr = (fri_amd._ptr(v) for v in (a, b, q, r))
+
+    def call():
+        rc = ctx.lib.fri_poly_div_rem(ctx.h, pa, a.size, pb, b.size, pq, q.size, ctypes.byref(lq), pr, r.size,
+                                      ctypes.byref(lr))
+        assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+    return call
+
+
+def transforms_ms(ctx, la, lb):
+    """Two fri_lde and one fri_interpolate at N = next_pow2(la + lb - 1)."""
+    log_n = max(0, (la + lb - 2).bit_length())
+    a, b, ys = coeffs(1, la), coeffs(2, lb), coeffs(3, 1 << log_n)
+    ev = np.empty(1 << log_n, dtype=np.uint32)
+    ln = ctypes.c_size_t()
+    pa, pb, py, pe = (fri_amd._ptr(v) for v in (a, b, ys, ev))
+
+    def call():
+        assert ctx.lib.fri_lde(ctx.h, pa, la, log_n, 1, pe) == 0
+        assert ctx.lib.fri_lde(ctx.h, pb, lb, log_n, 1, pe) == 0
+        assert ctx.lib.fri_interpolate(ctx.h, py, log_n, 1, pe, ctypes.byref(ln)) == 0
+    return median_ms(call), log_n
+
+
+def oracle_s(corc, kind, a, b):
+    """One run of the C oracle's schoolbook mul / div_rem (one thread), seconds."""
+    p64 = ctypes.POINTER(ctypes.c_uint64)
+    a64, b64 = np.ascontiguousarray(a.astype(np.uint64)), np.ascontiguousarray(b.astype(np.uint64))
+    o1 = np.zeros(a.size + b.size, dtype=np.uint64)
+    o2 = np.zeros(a.size + b.size, dtype=np.uint64)
+    t0 = time.perf_counter()
+    if kind == "mul":
+        corc.orc_poly_mul(a64.ctypes.data_as(p64), a.size, b64.ctypes.data_as(p64), b.size, o1.ctypes.data_as(p64), P)
+    else:
+        lq, lr = ctypes.c_size_t(), ctypes.c_size_t()
+        corc.orc_poly_div_rem(a64.ctypes.data_as(p64), a.size, b64.ctypes.data_as(p64), b.size,
+                              o1.ctypes.data_as(p64), ctypes.byref(lq), o2.ctypes.data_as(p64), ctypes.byref(lr), P)
+    return time.perf_counter() - t0
+
+
+def crossover(ctx):
+    say("(i) fri_poly_mul, direct kernel vs NTT path [ms, median of %d]; long operand 2^10 / 2^16 / 2^20" % REPS)
+    say("%8s  %10s %10s   %10s %10s   %10s %10s" % ("short", "direct", "ntt", "direct", "ntt", "direct", "ntt"))
+    best = {}
+    ls = 1
+    while ls <= fri_amd.POLY_DIRECT_LIMIT:
+        row = "%8d " % ls
+        for log_l in (10, 16, 20):
+            a, b = coeffs(100 + log_l, 1 << log_l), coeffs(200 + ls, ls)
+            fd, fn = mul_call(ctx, a, b, fri_amd.POLY_FORCE_DIRECT), mul_call(ctx, a, b, fri_amd.POLY_FORCE_NTT)
+            for _ in range(WARM):
+                fd()
+                fn()
+            td, tn = [], []
+            for _ in range(REPS):                                   # alternating
+                t0 = time.perf_counter()
+                fd()
+                t1 = time.perf_counter()
+                fn()
+                t2 = time.perf_counter()
+                td.append(t1 - t0)
+                tn.append(t2 - t1)
+            d, n = 1e3 * statistics.median(td), 1e3 * statistics.median(tn)
+            row += " %10.3f %10.3f  " % (d, n)
+            if d <= n and best.get(log_l, 0) == ls // 2:            # contiguous from 1
+                best[log_l] = ls
+        say(row)
+        ls *= 2
+    for log_l in (10, 16, 20):
+        say("largest short length (contiguous from 1) with direct <= ntt at long 2^%d: %d" % (log_l, best.get(log_l, 0)))
+    say("FRI_POLY_DIRECT_MAX in this build: %d" % fri_amd.POLY_DIRECT_MAX)
+
+
+def sizes(ctx, corc):
+    say()
+    say("(ii) whole calls [ms, median of %d]; oracle = C oracle schoolbook, one thread, one run" % REPS)
+    for la, lb in ((1 << 10, 1 << 10), (1 << 12, 1 << 12), (1 << 14, 1 << 14), (1 << 16, 1 << 16),
+                   (1 << 20, 1 << 20), (1 << 20, 2)):
+        a, b = coeffs(la, la), coeffs(la + lb, lb)
+        t = median_ms(mul_call(ctx, a, b, 0))
+        tt, log_n = transforms_ms(ctx, la, lb)
+        orc = "%8.3f s" % oracle_s(corc, "mul", a, b) if la * lb <= 1 << 28 else "   (skipped)"
+        say("mul      %8d x %-8d %9.3f ms   2 fri_lde + fri_interpolate at 2^%-2d %9.3f ms   oracle %s"
+            % (la, lb, t, log_n, tt, orc))
+    for la, lb in ((1 << 10, 1 << 10), (1 << 16, 1 << 16), (1 << 20, 1 << 20), (1 << 20, 2),
+                   ((1 << 11) - 1, 1 << 10), ((1 << 13) - 1, 1 << 12), ((1 << 15) - 1, 1 << 14),
+                   ((1 << 17) - 1, 1 << 16), ((1 << 21) - 1, 1 << 20)):
+        a, b = coeffs(3 * la, la), coeffs(5 * la + lb, lb)
+        t = median_ms(div_call(ctx, a, b))
+        tt, log_n = transforms_ms(ctx, la - lb + 1, lb)
+        orc = "%8.3f s" % oracle_s(corc, "div", a, b) if (la - lb + 1) * lb <= 1 << 28 else "   (skipped)"
+        say("div_rem  %8d / %-8d %9.3f ms   2 fri_lde + fri_interpolate at 2^%-2d %9.3f ms   oracle %s"
+            % (la, lb, t, log_n, tt, orc))
+    g = fo.fe_pow(5, (P - 1) >> 10, P)
+    for name, p, q in (("1023 o linear", coeffs(7, 1023), np.array([0, g], dtype=np.uint32)),
+                       ("2^10 o 2^6", coeffs(8, 1 << 10), coeffs(9, 1 << 6))):
+        t0 = time.perf_counter()
+        ctx.poly_compose(p, q)
+        first = 1e3 * (time.perf_counter() - t0)
+        t = median_ms(lambda: ctx.poly_compose(p, q))
+        say("compose  %-20s %9.3f ms   (first call %.3f ms; through the Python mirror)" % (name, t, first))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", help="also write the report to this file")
+    args = ap.parse_args()
+    ctx = fri_amd.Context(0, LOG_MAX)                              # raises without a gfx950 device
+    corc = fo.load_c_oracle()
+    corc.orc_set_num_threads(1)
+    say("poly_arith_probe: %s, context 2^%d" % (ctx.lib.fri_version().decode(), LOG_MAX))
+    crossover(ctx)
+    sizes(ctx, corc)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(_lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
