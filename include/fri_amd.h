@@ -195,6 +195,52 @@ int fri_poly_div_rem(fri_ctx* ctx, const uint32_t* a, size_t la, const uint32_t*
 int fri_poly_compose(fri_ctx* ctx, const uint32_t* p, size_t lp, const uint32_t* q, size_t lq,
                      uint32_t* out, size_t out_cap, size_t* len_out);
 
+/* ------------------------------------- polynomial from roots, Lagrange basis */
+/* src/polynomial/interpolation.rs on the device, with the conventions of the
+ * block above: host arrays, canonical values (a value >= p gives
+ * FRI_EINVAL), the needed length in *len_out when a capacity is too small,
+ * rank 0 on a multi-GPU context.  The reference multiplies the linear
+ * factors one by one (O(n^2)); here Z is a binary product tree: subtrees of
+ * FRI_ROOTS_LEAF roots are built by one workgroup each in LDS, and every
+ * level above is one batched set of cyclic NTT products, a fixed number of
+ * launches per level whatever its node count. */
+#define FRI_ROOTS_SMALL_LEAF 1u   /* test/measurement hook: leaf subtrees of 64 roots */
+/* Roots per LDS leaf subtree: the measured choice (profiles/poly_roots.txt,
+ * table (iii), from tools/poly_arith_probe.py --roots) — the power of two in
+ * 128..2048 with the lowest whole-call median at n = 2^16 (0.435 ms at 512
+ * against 0.448 at 256, 0.465 at 128, 0.520 at 1024 and 0.955 at 2048; 512
+ * in two runs).  At n = 2^20 the candidates 128, 256 and 512 lie within
+ * 0.012 ms of each other (0.981, 0.980, 0.992 ms), so the 2^16 winner stands. */
+#define FRI_ROOTS_LEAF       512
+#define FRI_LAGRANGE_MAX     4096
+
+/* Z(x) = prod_i (x - roots[i]) — gen_polynomial_from_roots
+ * (interpolation.rs:9-23).  n = 0 gives *len_out = 0 (Polynomial::zero(),
+ * :10-12); otherwise *len_out = n + 1: Z is monic and never trims.  Repeated
+ * roots and the roots 0 and p - 1 are ordinary inputs.  Any n with
+ * next_pow2(n) <= 2^log_n_max (the list is padded with zero roots to a power
+ * of two and the padding's factor x^pad is dropped from the result).
+ * flags: 0 or FRI_ROOTS_SMALL_LEAF. */
+int fri_poly_from_roots(fri_ctx* ctx, const uint32_t* roots, size_t n, uint32_t flags,
+                        uint32_t* out, size_t out_cap, size_t* len_out);
+
+/* L_i = Z/(x - xs[i]) / prod_{j!=i}(xs[i] - xs[j]) — gen_lagrange_polynomials
+ * (interpolation.rs:46-78; gen_lagrange_polynomials_parallel, :80-115, gives
+ * the same).  out is row-major n x n: row i holds L_i's coefficients
+ * x^0..x^(n-1), untrimmed.  n = 0 writes nothing.  A repeated x gives
+ * all-zero rows for every copy: the denominator is 0 and inverse(0) = 0
+ * (element.rs:54-57).  n <= FRI_LAGRANGE_MAX and out_cap >= n*n, else
+ * FRI_EINVAL; the n^2 words are built in the context's grown scratch (64 MiB
+ * at the limit).  Z from the product tree, the weights from the kernels of
+ * fri_interpolate_points, then one kernel of synthetic divisions that writes
+ * w_i * Z/(x - x_i) row by row. */
+int fri_lagrange_basis(fri_ctx* ctx, const uint32_t* xs, size_t n, uint32_t* out, size_t out_cap);
+
+/* Measurement hook (tools/poly_arith_probe.py): roots per leaf subtree of
+ * this context's later fri_poly_from_roots / fri_lagrange_basis calls, a
+ * power of two in 64..2048; 0 restores FRI_ROOTS_LEAF. */
+int fri_debug_set_roots_leaf(fri_ctx* ctx, uint32_t leaf);
+
 /* ---------------------------------------------------------------- FRI ops */
 /* One FRI fold of a layer of size m = 2^log_m living on the coset
  * layer_offset * <w_m> (natural order): out[i] = P'(x_i^2), i < m/2, with

@@ -4,6 +4,7 @@
 //   fri_ops.hip        kernel-level entry points: batch inverse, LDE,
 //                      interpolation, evaluation, fold, Merkle root
 //   fri_poly.hip       polynomial arithmetic: mul, div_rem, compose
+//   fri_roots.hip      polynomial from roots (product tree), Lagrange basis
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
@@ -246,6 +247,7 @@ struct fri_ctx {
     uint32_t commit_log_n = 0;      // codeword log2 of the resident commit
     uint32_t* interp_tmp = nullptr; // partials of fri_interpolate_points / fri_evaluate, fri_merkle_root's tree (grown on use)
     size_t interp_cap = 0;
+    uint32_t roots_leaf = 0;        // fri_debug_set_roots_leaf: roots per leaf subtree (0: FRI_ROOTS_LEAF)
     uint32_t* dq_host = nullptr;    // decommitment gather output: 64 KiB of coherent pinned host
     uint32_t* dq_dev = nullptr;     // memory the gather kernel writes directly (its device address)
     uint32_t* trace_tree = nullptr; // Merkle tree of the last fri_trace_commit LDE

@@ -62,6 +62,13 @@ struct NttPlan {
     const uint32_t* post_lo;     // optional output scale t^j (Montgomery, two-level)
     const uint32_t* post_hi;
     uint32_t* scratch;           // optional 2^log_n words the transform may use (2^24 coset LDE); else nullptr
+    // Batch (the product tree's levels, fri_roots.hip): 0 or 1 is one
+    // transform; else `batch` transforms in the same launches (grid y),
+    // transform b reading src + b*src_stride (d words each) and writing
+    // dst + b*dst_stride.  log_n >= 13 (whole tiles), strides multiples of 4
+    // words, batch <= 65535, no pre/post tables (they are indexed per transform).
+    uint32_t batch;
+    size_t src_stride, dst_stride;
 };
 // dst[k] = post(k) * sum_{j<d} src[j]*pre(j)*w^(jk); src may alias nothing in dst.
 void launch_ntt(const NttPlan& p, const uint32_t* src, size_t d, uint32_t* dst, hipStream_t s);
@@ -103,6 +110,25 @@ void launch_poly_conv_direct(const uint32_t* lng, size_t ll, const uint32_t* sht
 void launch_poly_reverse(const uint32_t* src, size_t top, size_t cnt, uint32_t* dst, size_t n, hipStream_t s);
 // r[i] = a[i] - t[i], i < n.
 void launch_poly_sub(const uint32_t* a, const uint32_t* t, uint32_t* r, size_t n, hipStream_t s);
+// Product tree and Lagrange rows (fri_roots.hip).  A level is 2^log_np words:
+// its monic nodes' low coefficients (Montgomery), side by side.
+// leaf: out = the level of nodes of degree 2^log_leaf (<= 2^ROOTS_LEAF_LOG_MAX)
+// over roots[0..n) padded with zero roots; canon: canonical output (the top).
+constexpr uint32_t ROOTS_LEAF_LOG_MAX = 11;
+void launch_roots_leaf(const uint32_t* roots, size_t n, uint32_t log_np, uint32_t log_leaf, bool canon, uint32_t* out,
+                       hipStream_t s);
+// one level, products of 2^lg <= 2^ROOTS_LDS_LOG_MAX words (nodes of degree 2^(lg-1) in, 2^lg out), in LDS
+constexpr uint32_t ROOTS_LDS_LOG_MAX = 12;
+void launch_roots_level_lds(const uint32_t* in, uint32_t* out, uint32_t log_np, uint32_t lg, bool canon,
+                            const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s);
+// out = ((a + s)(b + s) - 1) / 2^lg on `words` (a multiple of 4) transform values, s = (-1)^index
+void launch_roots_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t words, uint32_t lg, bool canon,
+                            hipStream_t s);
+// out[i*n + j] = w[i] * (Z / (x - xs[i]))[j], i, j < n; z: Z's n low coefficients (canonical, z_n = 1 implied),
+// w Montgomery; tmp: lagrange_tmp_words(n) words.
+size_t lagrange_tmp_words(size_t n);
+void launch_lagrange_rows(const uint32_t* xs, const uint32_t* z, const uint32_t* w, size_t n, uint32_t* out,
+                          uint32_t* tmp, hipStream_t s);
 struct DecommitPlan {
     uint64_t index;
     uint32_t log_n, n_layers;

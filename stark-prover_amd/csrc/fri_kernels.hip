@@ -81,7 +81,11 @@ __global__ __launch_bounds__(TPB) void k_ntt_pass(const uint32_t* src, size_t d,
                                                   uint32_t log_n, uint32_t s0, const uint32_t* __restrict__ tw,
                                                   const uint32_t* __restrict__ pre_lo, const uint32_t* __restrict__ pre_hi,
                                                   const uint32_t* __restrict__ post_lo,
-                                                  const uint32_t* __restrict__ post_hi) {
+                                                  const uint32_t* __restrict__ post_hi, size_t sstride,
+                                                  size_t dstride) {
+    // batch (NttPlan::batch): transform blockIdx.y of a launch; a single transform has gridDim.y == 1
+    src += (size_t)blockIdx.y * sstride;
+    dst += (size_t)blockIdx.y * dstride;
     // tile: 16 elements per thread; C columns (C consecutive words per row)
     constexpr uint32_t NS = A + B, P = 1u << NS, TILE = 16u * TPB, C = TILE / P;
     __shared__ uint32_t lds[TILE + TILE / 16 + 2 * (TILE >> 10)];
@@ -306,8 +310,11 @@ __global__ __launch_bounds__(TPB) void k_ntt_first_wide(const uint32_t* src, siz
                                                         const uint32_t* __restrict__ pre_lo,
                                                         const uint32_t* __restrict__ pre_hi,
                                                         const uint32_t* __restrict__ post_lo,
-                                                        const uint32_t* __restrict__ post_hi) {
+                                                        const uint32_t* __restrict__ post_hi, size_t sstride,
+                                                        size_t dstride) {
     static_assert(NS >= 9 && NS <= 12 && Z <= 3, "wide first pass: 9..12 stages");
+    src += (size_t)blockIdx.y * sstride;           // batch (NttPlan::batch): transform blockIdx.y
+    dst += (size_t)blockIdx.y * dstride;
     constexpr uint32_t P = 1u << NS, TILE = 16u * TPB, C = TILE / P;
     constexpr uint32_t VW = C < 4 ? C : 4;         // words per input vector (C consecutive words per row)
     constexpr uint32_t VPR = C / VW;               // input vectors per row
@@ -739,6 +746,8 @@ __global__ __launch_bounds__(512) void k_lde24_a(const uint32_t* __restrict__ a0
     oh[1] = make_uint4(hi[4], hi[5], hi[6], hi[7]);
 }
 
+static unsigned ntt_batch(const NttPlan& p) { return p.batch ? p.batch : 1u; }
+
 template <int NS>
 static void launch_first_wide(const uint32_t* src, size_t d, uint32_t* dst, uint32_t log_n, const NttPlan& p,
                               bool last, uint32_t z, hipStream_t s) {
@@ -749,8 +758,8 @@ static void launch_first_wide(const uint32_t* src, size_t d, uint32_t* dst, uint
     switch (z) {
 #define WIDE_CASE(ZV)                                                                                        \
     case ZV:                                                                                                 \
-        hipLaunchKernelGGL((k_ntt_first_wide<NS, TPB, ZV>), dim3(blocks), dim3(TPB), 0, s, src, d, dst, log_n, \
-                           p.tw, p.pre_lo, p.pre_hi, qlo, qhi);                                              \
+        hipLaunchKernelGGL((k_ntt_first_wide<NS, TPB, ZV>), dim3(blocks, ntt_batch(p)), dim3(TPB), 0, s, src, d, \
+                           dst, log_n, p.tw, p.pre_lo, p.pre_hi, qlo, qhi, p.src_stride, p.dst_stride);     \
         break;
         WIDE_CASE(0) WIDE_CASE(1) WIDE_CASE(2) default: WIDE_CASE(3)
 #undef WIDE_CASE
@@ -776,17 +785,18 @@ static void launch_pass(uint32_t ns, const uint32_t* src, size_t d, uint32_t* ds
     const uint32_t* phi = FIRST ? p.pre_hi : nullptr;
     const uint32_t* qlo = last ? p.post_lo : nullptr;
     const uint32_t* qhi = last ? p.post_hi : nullptr;
+    const size_t sst = FIRST ? p.src_stride : p.dst_stride;   // later passes run in place on dst
 #define NTT_CASE(NSV, AV, BV)                                                                                   \
     case NSV:                                                                                                   \
-        hipLaunchKernelGGL((k_ntt_pass<AV, BV, FIRST, TPB, (Z < AV ? Z : AV)>), dim3(blocks), dim3(TPB), 0, s, src, d, \
-                           dst, log_n, s0, p.tw, plo, phi, qlo, qhi);                                           \
+        hipLaunchKernelGGL((k_ntt_pass<AV, BV, FIRST, TPB, (Z < AV ? Z : AV)>), dim3(blocks, ntt_batch(p)), dim3(TPB), \
+                           0, s, src, d, dst, log_n, s0, p.tw, plo, phi, qlo, qhi, sst, p.dst_stride);          \
         break;
     // vector load/store phases: whole tiles of 32 contiguous columns, 16-byte aligned buffers
     const bool vec = NTT_VEC && ns == 8 && n >= 16u * TPB && (FIRST || s0 >= 2) &&
                      ((((uintptr_t)src) | ((uintptr_t)dst)) & 15u) == 0;
     if (vec) {
-        hipLaunchKernelGGL((k_ntt_pass<4, 4, FIRST, TPB, (Z < 4 ? Z : 4), true>), dim3(blocks), dim3(TPB), 0, s, src,
-                           d, dst, log_n, s0, p.tw, plo, phi, qlo, qhi);
+        hipLaunchKernelGGL((k_ntt_pass<4, 4, FIRST, TPB, (Z < 4 ? Z : 4), true>), dim3(blocks, ntt_batch(p)), dim3(TPB),
+                           0, s, src, d, dst, log_n, s0, p.tw, plo, phi, qlo, qhi, sst, p.dst_stride);
         return;
     }
     switch (ns) {
@@ -826,7 +836,7 @@ void launch_ntt(const NttPlan& p, const uint32_t* src, size_t d, uint32_t* dst, 
         hipLaunchKernelGGL(k_lde24_gather, dim3(256), dim3(256), 0, s, src, d, dst, p.pre_lo, p.pre_hi);
         hipLaunchKernelGGL(k_lde24_a, dim3(2048), dim3(512), 0, s, dst, p.scratch, p.tw);
         hipLaunchKernelGGL((k_ntt_pass<4, 4, false, 512, 0, true, true>), dim3(2048), dim3(512), 0, s, p.scratch,
-                           (size_t)0, dst, 24u, 16u, p.tw, nullptr, nullptr, nullptr, nullptr);
+                           (size_t)0, dst, 24u, 16u, p.tw, nullptr, nullptr, nullptr, nullptr, (size_t)0, (size_t)0);
         return;
     }
 #endif
@@ -1342,6 +1352,241 @@ void launch_poly_reverse(const uint32_t* src, size_t top, size_t cnt, uint32_t* 
 void launch_poly_sub(const uint32_t* a, const uint32_t* t, uint32_t* r, size_t n, hipStream_t s) {
     if (!n) return;
     hipLaunchKernelGGL(k_poly_sub, dim3(poly_blocks(n)), dim3(256), 0, s, a, t, r, n);
+}
+
+// ===================================== product tree and the Lagrange basis ==
+// fri_poly_from_roots / fri_lagrange_basis (fri_roots.hip; interpolation.rs:
+// 9-23, 46-115).  Z = prod (x - r_i) over 2^log_np roots (the list padded
+// with zero roots) as a binary product tree.  Every node is monic with the
+// leading 1 implicit: a node of degree m is its m low coefficients, in
+// Montgomery form, and a level is the 2^log_np words of its nodes side by side.
+//   (x^m + a)(x^m + b) = x^2m + (a + b) x^m + a b.
+//
+// Leaf kernel: one workgroup builds the subtree over 2^log_leaf consecutive
+// roots in LDS, level by level between two buffers.  A work item owns the
+// output coefficients k and m + k of one node: for i = 0..m-1 the term
+// a_i * b_((k - i) mod m) belongs to coefficient k when i <= k and to m + k
+// otherwise, so every item runs exactly m products; m + k also takes
+// a_k + b_k.  A level keeps its even nodes (the a's of the next level) in the
+// buffer's first half and the odd nodes in the second: consecutive lanes then
+// read one a word (a broadcast) or, below m = 64, words of neighbouring nodes
+// that lie side by side, and consecutive b words (mod m): no two lanes of a
+// wave meet in a bank at different addresses.  Sums of <= 2^10 Montgomery
+// products (< 2^32 each) stay below 2^42 in 64 bits and are reduced once.
+// LDS: two buffers of the 2048-word limit, 16 KiB: ten workgroups per CU.
+__global__ __launch_bounds__(256) void k_roots_leaf(const uint32_t* __restrict__ roots, size_t n, uint32_t log_leaf,
+                                                    uint32_t canon, uint32_t* __restrict__ out) {
+    __shared__ uint32_t buf[2][1u << ROOTS_LEAF_LOG_MAX];
+    const uint32_t L = 1u << log_leaf, H = L >> 1, tid = threadIdx.x;
+    const size_t r0 = (size_t)blockIdx.x << log_leaf;
+    // level 0: node i is the constant -r_i; even nodes first
+    for (uint32_t i = tid; i < L; i += blockDim.x) {
+        const uint32_t r = r0 + i < n ? roots[r0 + i] : 0u;
+        buf[0][log_leaf ? (i & 1u) * H + (i >> 1) : 0u] = to_mont(neg(r));
+    }
+    uint32_t cur = 0;
+    for (uint32_t lm = 0; lm < log_leaf; lm++, cur ^= 1u) {
+        const uint32_t m = 1u << lm;
+        const uint32_t* a = buf[cur];          // node j of the even half, m words at j*m
+        const uint32_t* b = buf[cur] + H;
+        uint32_t* dst = buf[cur ^ 1u];
+        __syncthreads();
+        for (uint32_t t = tid; t < H; t += blockDim.x) {
+            const uint32_t node = t >> lm, k = t & (m - 1);
+            const uint32_t* an = a + node * m;
+            const uint32_t* bn = b + node * m;
+            uint64_t lo = 0, hi = 0;
+            for (uint32_t i = 0; i < m; i++) {
+                const uint64_t p = mmul(an[i], bn[(k - i) & (m - 1)]);
+                lo += i <= k ? p : 0;
+                hi += i <= k ? 0 : p;
+            }
+            const uint32_t clo = mmul(redc(lo), R2_MOD_P);
+            const uint32_t chi = add(mmul(redc(hi), R2_MOD_P), add(an[k], bn[k]));
+            // output node `node` (2m words): even nodes in the first half; the
+            // last level's single node fills the whole buffer
+            uint32_t* o = dst + (lm + 1 < log_leaf ? (node & 1u) * H + (node >> 1) * 2 * m : 0u);
+            o[k] = clo;
+            o[m + k] = chi;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < L; i += blockDim.x) out[r0 + i] = canon ? from_mont(buf[cur][i]) : buf[cur][i];
+}
+void launch_roots_leaf(const uint32_t* roots, size_t n, uint32_t log_np, uint32_t log_leaf, bool canon, uint32_t* out,
+                       hipStream_t s) {
+    const uint32_t half = log_leaf ? 1u << (log_leaf - 1) : 1u;
+    const uint32_t tpb = half < 64 ? 64 : half > 256 ? 256 : half;
+    hipLaunchKernelGGL(k_roots_leaf, dim3(1u << (log_np - log_leaf)), dim3(tpb), 0, s, roots, n, log_leaf,
+                       canon ? 1u : 0u, out);
+}
+
+// One level above the leaves whose products (2m = 2^lg words) fit LDS: a
+// workgroup takes a tile of `tile` consecutive words of the level (tile / 2m
+// pairs of nodes), and the whole tile runs as one batched transform, because
+// the stages s < lg of a DIT over the tile are independent transforms of its
+// aligned 2^lg blocks (the twiddles are stage-packed, size-independent).
+// a and b of a pair are gathered bit-reversed into two arrays, zero-padded to
+// 2m (the odd positions: stage 0 is then a copy), transformed, multiplied as
+// (A + s)(B + s) - 1 with s = x^m at w_2m^k = (-1)^k (the monic factors; the
+// product's x^2m wraps to the constant 1), scaled by (2m)^-1, scattered
+// bit-reversed, transformed back and stored: one launch per level, no
+// intermediate in HBM.  `scale` is Montgomery((2m)^-1), or the canonical
+// value when the level is the top and leaves canonical coefficients.
+__device__ __forceinline__ void roots_stage(uint32_t* v, uint32_t tile, uint32_t s, const uint32_t* __restrict__ tw) {
+    const uint32_t h = 1u << s;
+    for (uint32_t e = threadIdx.x; e < tile / 2; e += blockDim.x) {
+        const uint32_t lo = e & (h - 1), i = ((e >> s) << (s + 1)) | lo;
+        const uint32_t u = v[i], t = mmul(v[i + h], tw[h + lo]);
+        v[i] = add(u, t);
+        v[i + h] = sub(u, t);
+    }
+}
+__global__ __launch_bounds__(256) void k_roots_level(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                     uint32_t tile, uint32_t lg, const uint32_t* __restrict__ tw_f,
+                                                     const uint32_t* __restrict__ tw_i, uint32_t scale) {
+    __shared__ uint32_t A[1u << ROOTS_LDS_LOG_MAX], B[1u << ROOTS_LDS_LOG_MAX];
+    const uint32_t tid = threadIdx.x, m = 1u << (lg - 1), mask = 2 * m - 1;
+    const size_t base = (size_t)blockIdx.x * tile;
+    for (uint32_t e = tid; e < tile; e += 256) {
+        const uint32_t r = e & mask, i = r & (m - 1);
+        const uint32_t pos = (e & ~mask) + (__brev(i) >> (32 - lg));   // even: i < m
+        const uint32_t v = in[base + e];
+        uint32_t* dstv = r < m ? A : B;
+        dstv[pos] = v;
+        dstv[pos + 1] = v;                                          // stage 0 against the zero padding
+    }
+    for (uint32_t s = 1; s < lg; s++) {
+        __syncthreads();
+        roots_stage(A, tile, s, tw_f);
+        roots_stage(B, tile, s, tw_f);
+    }
+    __syncthreads();
+    uint32_t r[(1u << ROOTS_LDS_LOG_MAX) / 256];
+#pragma unroll
+    for (uint32_t k = 0; k < (1u << ROOTS_LDS_LOG_MAX) / 256; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e >= tile) continue;
+        const uint32_t sg = (e & 1u) ? P - R_MOD_P : R_MOD_P;
+        r[k] = mmul(sub(mmul(add(A[e], sg), add(B[e], sg)), R_MOD_P), scale);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < (1u << ROOTS_LDS_LOG_MAX) / 256; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e < tile) A[(e & ~mask) + (__brev(e & mask) >> (32 - lg))] = r[k];
+    }
+    for (uint32_t s = 0; s < lg; s++) {
+        __syncthreads();
+        roots_stage(A, tile, s, tw_i);
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < tile; e += 256) out[base + e] = A[e];
+}
+void launch_roots_level_lds(const uint32_t* in, uint32_t* out, uint32_t log_np, uint32_t lg, bool canon,
+                            const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s) {
+    const uint32_t tile = log_np < ROOTS_LDS_LOG_MAX ? 1u << log_np : 1u << ROOTS_LDS_LOG_MAX;
+    const uint32_t ninv = inv_std(1u << lg);
+    hipLaunchKernelGGL(k_roots_level, dim3((unsigned)(((size_t)1 << log_np) / tile)), dim3(256), 0, s, in, out, tile, lg,
+                       tw_fwd, tw_inv, canon ? ninv : to_mont(ninv));
+}
+
+// Larger levels: the transforms are batched launches of the NTT passes
+// (NttPlan::batch), and this is the pointwise step between them, elementwise
+// over the level because k mod 2 is the word index mod 2: out = ((A + s)(B + s)
+// - 1) * scale, A and B the transforms of the even and the odd nodes.
+__global__ __launch_bounds__(256) void k_roots_pointwise(const uint4* __restrict__ a, const uint4* __restrict__ b,
+                                                         uint4* __restrict__ out, size_t n4, uint32_t scale) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    auto pw = [&](uint32_t x, uint32_t y, uint32_t sg) {
+        return mmul(sub(mmul(add(x, sg), add(y, sg)), R_MOD_P), scale);
+    };
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 x = a[i], y = b[i];
+        uint4 r;
+        r.x = pw(x.x, y.x, R_MOD_P);
+        r.y = pw(x.y, y.y, P - R_MOD_P);
+        r.z = pw(x.z, y.z, R_MOD_P);
+        r.w = pw(x.w, y.w, P - R_MOD_P);
+        out[i] = r;
+    }
+}
+void launch_roots_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* out, size_t words, uint32_t lg, bool canon,
+                            hipStream_t s) {
+    const uint32_t ninv = inv_std((uint32_t)(((size_t)1 << lg) % P));
+    hipLaunchKernelGGL(k_roots_pointwise, dim3(poly_blocks(words / 4)), dim3(256), 0, s,
+                       reinterpret_cast<const uint4*>(a), reinterpret_cast<const uint4*>(b),
+                       reinterpret_cast<uint4*>(out), words / 4, canon ? ninv : to_mont(ninv));
+}
+
+// Lagrange rows: L_i = w_i * Z / (x - x_i), the quotient by synthetic
+// division, q_i[n-1] = 1, q_i[j-1] = z_j + x_i q_i[j].  A wave takes 64 rows
+// (one lane each) and a segment of LAGRANGE_SEG columns, 64 columns at a
+// time: the lanes run the chain downwards and put w_i q_i[j] into an LDS tile
+// (row stride 65 words: 64 banks, no conflict), then the tile goes out row by
+// row, 64 consecutive words (256 bytes) per store instruction, instead of 64
+// stores at stride n.  The chain of segment [c0, c1) starts from
+//   q_i[c1 - 1] = T(c1),  T(c) = sum_{k >= c} z_k x_i^(k - c)  (z_n = 1),
+// which the lane folds together from the segment values P_s(x_i) of a first
+// kernel (P_s the slice of Z on segment s): T(s SEG) = P_s + x^len_s T(end_s).
+constexpr uint32_t LAGRANGE_SEG = 256;
+static uint32_t lagrange_segments(size_t n) {
+    return n >= 1024 ? (uint32_t)((n + LAGRANGE_SEG - 1) / LAGRANGE_SEG) : 1u;
+}
+size_t lagrange_tmp_words(size_t n) { return (size_t)(lagrange_segments(n) - 1) * n; }
+__global__ __launch_bounds__(256) void k_lagrange_parts(const uint32_t* __restrict__ xs, const uint32_t* __restrict__ z,
+                                                        uint32_t n, uint32_t* __restrict__ part) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, sgm = blockIdx.y + 1;
+    if (i >= n) return;
+    const uint32_t lo = sgm * LAGRANGE_SEG, hi = lo + LAGRANGE_SEG < n ? lo + LAGRANGE_SEG : n;
+    const uint32_t xm = to_mont(xs[i]);
+    uint32_t h = 0;
+    for (uint32_t k = hi; k-- > lo;) h = add(mmul(h, xm), z[k]);
+    part[(size_t)(sgm - 1) * n + i] = h;
+}
+__global__ __launch_bounds__(64) void k_lagrange_rows(const uint32_t* __restrict__ xs, const uint32_t* __restrict__ z,
+                                                      const uint32_t* __restrict__ w, uint32_t n,
+                                                      const uint32_t* __restrict__ part, uint32_t* __restrict__ out) {
+    __shared__ uint32_t tile[64 * 65];
+    __shared__ uint32_t zs[64];
+    const uint32_t lane = threadIdx.x, row0 = blockIdx.x * 64, i = row0 + lane;
+    const uint32_t sgm = blockIdx.y, S = gridDim.y;
+    const uint32_t c0 = S > 1 ? sgm * LAGRANGE_SEG : 0u;
+    const uint32_t c1 = S > 1 && c0 + LAGRANGE_SEG < n ? c0 + LAGRANGE_SEG : n;
+    const uint32_t xm = i < n ? to_mont(xs[i]) : 0u, wm = i < n ? w[i] : 0u;
+    uint32_t q = 1u;                                                // T(n) = z_n
+    if (i < n && c1 < n) {
+        const uint32_t xseg = mpow(xm, LAGRANGE_SEG);
+        for (uint32_t sp = S - 1; sp > sgm; sp--) {
+            const uint32_t len = n - sp * LAGRANGE_SEG < LAGRANGE_SEG ? n - sp * LAGRANGE_SEG : LAGRANGE_SEG;
+            q = add(part[(size_t)(sp - 1) * n + i], mmul(q, len == LAGRANGE_SEG ? xseg : mpow(xm, len)));
+        }
+    }
+    for (int cb = (int)((c1 - 1) & ~63u); cb >= (int)c0; cb -= 64) {
+        const uint32_t ce = (uint32_t)cb + 64 < c1 ? (uint32_t)cb + 64 : c1;
+        zs[lane] = (uint32_t)cb + lane < ce ? z[cb + lane] : 0u;
+        __syncthreads();
+        for (int j = (int)ce - 1; j >= cb; j--) {
+            tile[lane * 65 + (j - cb)] = mmul(q, wm);               // w_i q_i[j], canonical
+            q = add(zs[j - cb], mmul(q, xm));                       // q_i[j - 1]
+        }
+        __syncthreads();
+        if ((uint32_t)cb + lane < ce) {
+            const uint32_t rows = n - row0 < 64 ? n - row0 : 64;
+            for (uint32_t r = 0; r < rows; r++) out[(size_t)(row0 + r) * n + cb + lane] = tile[r * 65 + lane];
+        }
+        __syncthreads();
+    }
+}
+void launch_lagrange_rows(const uint32_t* xs, const uint32_t* z, const uint32_t* w, size_t n, uint32_t* out,
+                          uint32_t* tmp, hipStream_t s) {
+    if (!n) return;
+    const uint32_t S = lagrange_segments(n);
+    if (S > 1)
+        hipLaunchKernelGGL(k_lagrange_parts, dim3((unsigned)((n + 255) / 256), S - 1), dim3(256), 0, s, xs, z,
+                           (uint32_t)n, tmp);
+    hipLaunchKernelGGL(k_lagrange_rows, dim3((unsigned)((n + 63) / 64), S), dim3(64), 0, s, xs, z, w, (uint32_t)n, tmp,
+                       out);
 }
 
 }  // namespace fri

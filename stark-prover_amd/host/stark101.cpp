@@ -844,6 +844,38 @@ Poly Polynomial<P>::compose(const Polynomial<P>& other) const {
     return Poly(to_fe(out.data(), len));
 }
 
+// ---- interpolation.rs:9-115 on the device ----------------------------------
+template <>
+Poly gen_polynomial_from_roots<P>(const std::vector<FE>& roots) {
+    if (roots.empty()) return Poly::zero();                     // interpolation.rs:10-12
+    auto gpu = Gpu::thread_default(ceil_log2(roots.size()));
+    const auto r = to_u32(roots);
+    std::vector<uint32_t> out(r.size() + 1);
+    size_t len = 0;
+    gpu->check(fri_poly_from_roots(gpu->ctx(), r.data(), r.size(), 0, out.data(), out.size(), &len),
+               "fri_poly_from_roots");
+    return Poly(to_fe(out.data(), len));
+}
+
+template <>
+std::vector<Poly> gen_lagrange_polynomials<P>(const std::vector<FE>& xs) {
+    const size_t n = xs.size();
+    std::vector<Poly> rows;
+    if (n == 0) return rows;
+    auto gpu = Gpu::thread_default(ceil_log2(n));
+    const auto x = to_u32(xs);
+    std::vector<uint32_t> out(n * n);
+    gpu->check(fri_lagrange_basis(gpu->ctx(), x.data(), n, out.data(), out.size()), "fri_lagrange_basis");
+    rows.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        // scalar_mul does not re-trim (ops.rs:194-198): n coefficients under
+        // degree n - 1, also for the all-zero row of a repeated x
+        rows[i].coefficients = to_fe(out.data() + i * n, n);
+        rows[i].degree = static_cast<int64_t>(n) - 1;
+    }
+    return rows;
+}
+
 std::vector<FE> batch_inverse(const std::vector<FE>& xs) {
     if (xs.empty()) return {};
     auto gpu = Gpu::thread_default(ceil_log2(xs.size()));

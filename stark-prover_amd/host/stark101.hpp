@@ -262,6 +262,47 @@ Polynomial<M> Polynomial<M>::compose(const Polynomial& other) const {
     return result;
 }
 
+// ------------------------------------------------------------- interpolation
+// interpolation.rs:9-115.  A general modulus takes the reference's schoolbook
+// algorithms below, on the host; the frozen field (Poly) has explicit
+// specialisations that always run on the device (fri_poly_from_roots /
+// fri_lagrange_basis through Gpu::thread_default).  Like the reference's
+// scalar_mul (ops.rs:194-198) the basis polynomials are not re-trimmed: the
+// L_i of a repeated x_i (denominator 0, inverse(0) = 0) is n zero
+// coefficients under degree n - 1.
+template <uint64_t M>
+Polynomial<M> gen_polynomial_from_roots(const std::vector<FieldElement<M>>& roots) {   // interpolation.rs:9-23
+    using FE = FieldElement<M>;
+    if (roots.empty()) return Polynomial<M>::zero();
+    Polynomial<M> p(std::vector<FE>{FE::one()});
+    for (const FE& r : roots) p.mul_assign(Polynomial<M>(std::vector<FE>{-r, FE::one()}));
+    return p;
+}
+
+template <uint64_t M>
+std::vector<Polynomial<M>> gen_lagrange_polynomials(const std::vector<FieldElement<M>>& xs) {   // interpolation.rs:46-78
+    using FE = FieldElement<M>;
+    std::vector<Polynomial<M>> out;
+    if (xs.empty()) return out;
+    const Polynomial<M> Z = gen_polynomial_from_roots<M>(xs);
+    out.reserve(xs.size());
+    for (size_t i = 0; i < xs.size(); i++) {
+        FE denom = FE::one();
+        for (size_t j = 0; j < xs.size(); j++)
+            if (j != i) denom *= xs[i] - xs[j];
+        auto qr = Z.div_rem(Polynomial<M>(std::vector<FE>{-xs[i], FE::one()}));
+        if (!qr.second.is_zero()) throw Panic("Z(x) should be divisible by (x - x_i)");   // :69-71, cannot fire
+        qr.first.scalar_mul(denom.inverse());
+        out.push_back(std::move(qr.first));
+    }
+    return out;
+}
+
+template <uint64_t M>
+std::vector<Polynomial<M>> gen_lagrange_polynomials_parallel(const std::vector<FieldElement<M>>& roots) {   // :80-115
+    return gen_lagrange_polynomials<M>(roots);
+}
+
 // ------------------------------------------------------------------ CosetFri
 // coset_fri.rs:9-36: D = { offset * omega^i : i < domain_size }.
 template <uint64_t M>
@@ -360,6 +401,11 @@ template <>
 std::pair<Polynomial<P>, Polynomial<P>> Polynomial<P>::div_rem(const Polynomial<P>& rhs) const;
 template <>
 Polynomial<P> Polynomial<P>::compose(const Polynomial<P>& other) const;
+// ... and so do its vanishing polynomial and Lagrange basis (n <= FRI_LAGRANGE_MAX)
+template <>
+Polynomial<P> gen_polynomial_from_roots<P>(const std::vector<FieldElement<P>>& roots);
+template <>
+std::vector<Polynomial<P>> gen_lagrange_polynomials<P>(const std::vector<FieldElement<P>>& xs);
 
 // omega_n = g^((p-1)/n) (frozen spec), n a power of two <= 2^30.
 FE omega(uint32_t log_n);

@@ -47,6 +47,9 @@ POLY_FORCE_NTT = 1        # FRI_POLY_FORCE_* (fri_amd.h): fri_poly_mul's test/me
 POLY_FORCE_DIRECT = 2
 POLY_DIRECT_LIMIT = 4096  # FRI_POLY_DIRECT_LIMIT: the direct kernel's hard limit (short operand)
 POLY_DIRECT_MAX = 1024    # FRI_POLY_DIRECT_MAX: fri_poly_mul's measured crossover to the direct kernel
+ROOTS_SMALL_LEAF = 1      # FRI_ROOTS_SMALL_LEAF: fri_poly_from_roots' test/measurement hook (leaves of 64 roots)
+ROOTS_LEAF = 512          # FRI_ROOTS_LEAF: roots per LDS leaf subtree of the product tree
+LAGRANGE_MAX = 4096       # FRI_LAGRANGE_MAX: fri_lagrange_basis' largest n
 
 
 class FriError(RuntimeError):
@@ -118,6 +121,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_poly_div_rem": (i32, [vp, pu32, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz), pu32, sz,
                                    ctypes.POINTER(sz)]),
         "fri_poly_compose": (i32, [vp, pu32, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz)]),
+        "fri_poly_from_roots": (i32, [vp, pu32, sz, u32, pu32, sz, ctypes.POINTER(sz)]),
+        "fri_lagrange_basis": (i32, [vp, pu32, sz, pu32, sz]),
+        "fri_debug_set_roots_leaf": (i32, [vp, u32]),
         "fri_fold": (i32, [vp, pu32, u32, u32, u32, pu32]),
         "fri_merkle_root": (i32, [vp, pu32, sz, ctypes.c_char_p]),
         "fri_commit": (i32, [vp, pu32, sz, u32, u32, ctypes.POINTER(ChannelState), u32, pu32,
@@ -372,6 +378,34 @@ class Context:
         self._check(self.lib.fri_poly_compose(self.h, _ptr(x), x.size, _ptr(y), y.size, _ptr(out), out.size,
                                               ctypes.byref(ln)))
         return out[: ln.value]
+
+    def poly_from_roots(self, roots, small_leaf: bool = False) -> np.ndarray:
+        """Z(x) = prod (x - r) over `roots` (gen_polynomial_from_roots,
+        interpolation.rs:9-23; fri_poly_from_roots): n + 1 coefficients, monic;
+        no roots give the zero polynomial (length 0).  small_leaf: the
+        FRI_ROOTS_SMALL_LEAF hook (leaf subtrees of 64 roots)."""
+        r = _u32(roots)
+        out = np.empty(r.size + 1, dtype=np.uint32)
+        ln = ctypes.c_size_t()
+        self._check(self.lib.fri_poly_from_roots(self.h, _ptr(r), r.size, ROOTS_SMALL_LEAF if small_leaf else 0,
+                                                 _ptr(out), out.size, ctypes.byref(ln)))
+        return out[: ln.value]
+
+    def lagrange_basis(self, xs) -> np.ndarray:
+        """The Lagrange basis over `xs` (gen_lagrange_polynomials,
+        interpolation.rs:46-78; fri_lagrange_basis): shape (n, n), row i the
+        coefficients x^0..x^(n-1) of L_i, untrimmed; the rows of a repeated x
+        are zero.  n <= LAGRANGE_MAX."""
+        x = _u32(xs)
+        out = np.empty((x.size, x.size), dtype=np.uint32)
+        self._check(self.lib.fri_lagrange_basis(self.h, _ptr(x), x.size, _ptr(out), out.size))
+        return out
+
+    def set_roots_leaf(self, leaf: int):
+        """Measurement hook (fri_debug_set_roots_leaf): roots per leaf subtree
+        of this context's later poly_from_roots / lagrange_basis calls; 0
+        restores ROOTS_LEAF."""
+        self._check(self.lib.fri_debug_set_roots_leaf(self.h, leaf))
 
     def fold(self, layer, layer_offset: int, beta: int) -> np.ndarray:
         v = _u32(layer)
@@ -1246,6 +1280,24 @@ def poly_compose(p, q, ctx: Optional[Context] = None) -> np.ndarray:
     """Polynomial::compose (ops.rs:214-237) on the device: p(q(x))."""
     ctx = ctx or _default_ctx(_log_for(max(1, len(p)) * max(1, len(q))))
     return ctx.poly_compose(p, q)
+
+
+# ---- src/polynomial/interpolation.rs ----------------------------------------
+def gen_polynomial_from_roots(roots, ctx: Optional[Context] = None) -> np.ndarray:
+    """gen_polynomial_from_roots (interpolation.rs:9-23) on the device:
+    prod (x - r), n + 1 coefficients; the zero polynomial for no roots."""
+    ctx = ctx or _default_ctx(_log_for(max(1, len(roots))))
+    return ctx.poly_from_roots(roots)
+
+
+def gen_lagrange_polynomials(xs, ctx: Optional[Context] = None) -> np.ndarray:
+    """gen_lagrange_polynomials (interpolation.rs:46-78) on the device: the
+    (n, n) array whose row i holds L_i's coefficients, untrimmed."""
+    ctx = ctx or _default_ctx(_log_for(max(1, len(xs))))
+    return ctx.lagrange_basis(xs)
+
+
+gen_lagrange_polynomials_parallel = gen_lagrange_polynomials   # interpolation.rs:80-115: the same polynomials
 
 
 def fri_commit(coeffs: Sequence[int], log_n: int, channel: Channel, offset: int = GENERATOR,

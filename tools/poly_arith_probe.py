@@ -11,9 +11,17 @@
       fri_interpolate at the product's transform size (the same three
       transforms through existing entry points).
 
+ (iii) with --roots FILE, instead of (i) and (ii): fri_poly_from_roots for
+      every candidate leaf size (fri_debug_set_roots_leaf) at 2^10, 2^14, 2^16
+      and 2^20 roots, beside the C oracle's orc_poly_from_roots up to 2^14 and
+      beside 2^10 successive fri_poly_mul by a linear factor (the only device
+      route before fri_poly_from_roots); and fri_lagrange_basis at n = 256,
+      1024 and 4096, beside the device-to-host copy of its n^2 words alone.
+      This is the table behind FRI_ROOTS_LEAF (profiles/poly_roots.txt).
+
 Every figure is the median of REPS synchronous C-ABI calls after WARM
 warm-ups, host clock around the call (uploads and read-back included).
-Shapes are seeded.  Usage: poly_arith_probe.py [--out FILE]"""
+Shapes are seeded.  Usage: poly_arith_probe.py [--out FILE | --roots FILE]"""
 import argparse
 import ctypes
 import os
@@ -176,19 +184,114 @@ def sizes(ctx, corc):
         say("compose  %-20s %9.3f ms   (first call %.3f ms; through the Python mirror)" % (name, t, first))
 
 
+ROOTS_LEAVES = (128, 256, 512, 1024, 2048)
+
+
+def roots_call(ctx, r):
+    out = np.empty(r.size + 1, dtype=np.uint32)
+    ln = ctypes.c_size_t()
+    pr, po = fri_amd._ptr(r), fri_amd._ptr(out)
+
+    def call():
+        rc = ctx.lib.fri_poly_from_roots(ctx.h, pr, r.size, 0, po, out.size, ctypes.byref(ln))
+        assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+    return call, out
+
+
+def d2h_ms(words):
+    """A plain device-to-host hipMemcpy of `words` words into pageable memory."""
+    hip = ctypes.CDLL("libamdhip64.so")
+    dev = ctypes.c_void_p()
+    assert hip.hipMalloc(ctypes.byref(dev), ctypes.c_size_t(words * 4)) == 0
+    host = np.empty(words, dtype=np.uint32)
+    t = median_ms(lambda: hip.hipMemcpy(host.ctypes.data_as(ctypes.c_void_p), dev, ctypes.c_size_t(words * 4), 2))
+    hip.hipFree(dev)
+    return t
+
+
+def roots(ctx, corc):
+    p64 = ctypes.POINTER(ctypes.c_uint64)
+    corc.orc_poly_from_roots.restype = ctypes.c_size_t
+    corc.orc_poly_from_roots.argtypes = [p64, ctypes.c_size_t, p64, ctypes.c_uint64]
+    say("(iii) fri_poly_from_roots, whole call [ms, median of %d] per leaf size (roots per LDS leaf subtree)" % REPS)
+    say("%8s " % "n" + "".join(" %9d" % lf for lf in ROOTS_LEAVES) + "   oracle (one thread, one run)")
+    best = {}
+    for log_n in (10, 14, 16, 20):
+        n = 1 << log_n
+        r = coeffs(900 + log_n, n)
+        call, out = roots_call(ctx, r)
+        ts = {lf: [] for lf in ROOTS_LEAVES}
+        for lf in ROOTS_LEAVES:
+            ctx.set_roots_leaf(lf)
+            for _ in range(WARM):
+                call()
+        for _ in range(REPS):                                       # the candidates alternate
+            for lf in ROOTS_LEAVES:
+                ctx.set_roots_leaf(lf)
+                t0 = time.perf_counter()
+                call()
+                ts[lf].append(time.perf_counter() - t0)
+        med = {lf: 1e3 * statistics.median(ts[lf]) for lf in ROOTS_LEAVES}
+        best[log_n] = min(ROOTS_LEAVES, key=lambda lf: med[lf])
+        orc = "   (skipped)"
+        if log_n <= 14:
+            r64 = np.ascontiguousarray(r.astype(np.uint64))
+            o64 = np.zeros(n + 1, dtype=np.uint64)
+            t0 = time.perf_counter()
+            corc.orc_poly_from_roots(r64.ctypes.data_as(p64), n, o64.ctypes.data_as(p64), P)
+            orc = "%9.3f s" % (time.perf_counter() - t0)
+            assert np.array_equal(out.astype(np.uint64), o64)
+        say("%8d " % n + "".join(" %9.3f" % med[lf] for lf in ROOTS_LEAVES) + "   " + orc)
+    ctx.set_roots_leaf(0)
+    for log_n in (16, 20):
+        say("lowest median at n = 2^%d: leaf %d" % (log_n, best[log_n]))
+    say("FRI_ROOTS_LEAF in this build: %d (the 2^16 winner when the two differ)" % fri_amd.ROOTS_LEAF)
+    # the parent's only device route: one fri_poly_mul by (x - r) per root
+    r = coeffs(910, 1 << 10)
+
+    def chain():
+        acc = np.array([1], dtype=np.uint32)
+        for v in r:
+            acc = ctx.poly_mul(acc, np.array([(P - int(v)) % P, 1], dtype=np.uint32))
+        return acc
+    t0 = time.perf_counter()
+    z = chain()
+    t = 1e3 * (time.perf_counter() - t0)
+    assert np.array_equal(z, ctx.poly_from_roots(r))
+    say("n = 1024 as 1024 successive fri_poly_mul by a linear factor (Python mirror, one run): %9.3f ms" % t)
+    say()
+    say("fri_lagrange_basis, whole call [ms, median of %d]; copy = a device-to-host hipMemcpy of n^2 words alone" % REPS)
+    for n in (256, 1024, 4096):
+        xs = np.unique(coeffs(920 + n, n + 64))[:n].astype(np.uint32)
+        xs = np.ascontiguousarray(xs[np.random.default_rng(n).permutation(n)])
+        out = np.empty((n, n), dtype=np.uint32)
+        px, po = fri_amd._ptr(xs), fri_amd._ptr(out)
+
+        def call():
+            rc = ctx.lib.fri_lagrange_basis(ctx.h, px, n, po, out.size)
+            assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+        t, c = median_ms(call), d2h_ms(n * n)
+        say("n = %5d  call %9.3f ms   copy %9.3f ms   call - copy %9.3f ms" % (n, t, c, t - c))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", help="also write the report to this file")
+    ap.add_argument("--roots", metavar="FILE", help="run the from_roots / Lagrange section (iii) alone and write it here")
     args = ap.parse_args()
     ctx = fri_amd.Context(0, LOG_MAX)                              # raises without a gfx950 device
     corc = fo.load_c_oracle()
     corc.orc_set_num_threads(1)
     say("poly_arith_probe: %s, context 2^%d" % (ctx.lib.fri_version().decode(), LOG_MAX))
-    crossover(ctx)
-    sizes(ctx, corc)
+    if args.roots:
+        roots(ctx, corc)
+    else:
+        crossover(ctx)
+        sizes(ctx, corc)
     ctx.close()
-    if args.out:
-        with open(args.out, "w") as f:
+    out = args.roots or args.out
+    if out:
+        with open(out, "w") as f:
             f.write("\n".join(_lines) + "\n")
 
 
