@@ -39,10 +39,10 @@ def split_levels(nodes, m):
         m >>= 1
 
 
-def oracle_commit_full(corc, oracle, coeffs, log_n, offset=5, state=None):
-    """The C oracle's commit of `coeffs` on offset * <w_{2^log_n}>, with all it
-    stores: .res (OrcFriResult), .n_layers, .roots (bytes), .betas,
-    .final_value, .final_degree, .state (hex), and per layer k
+def oracle_commit_full(corc, oracle, coeffs, log_n, offset=5, state=None, forced_betas=None):
+    """The C oracle's commit of `coeffs` on offset * <w_{2^log_n}> (with
+    `forced_betas` in place of the channel's, if given), with all it stores:
+    .res (OrcFriResult), .n_layers, .roots (bytes), .betas, .final_value, .final_degree, .state (hex), and per layer k
     .values[k] (uint32, n >> k) and .levels[k][l] (uint8, (n >> k >> l, 32))."""
     n = 1 << log_n
     c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.uint64))
@@ -56,8 +56,10 @@ def oracle_commit_full(corc, oracle, coeffs, log_n, offset=5, state=None):
         och.state = st.encode()
         och.state_len = 64
     res = oracle.OrcFriResult()
+    fb = None if forced_betas is None else np.ascontiguousarray(np.asarray(forced_betas, dtype=np.uint64))
     rc = corc.orc_fri_commit_fast(c.ctypes.data_as(P64), c.size, log_n, offset, oracle.GEN, oracle.P,
-                                  ctypes.byref(och), None, ctypes.byref(res), layers_out.ctypes.data_as(P64),
+                                  ctypes.byref(och), None if fb is None else fb.ctypes.data_as(P64),
+                                  ctypes.byref(res), layers_out.ctypes.data_as(P64),
                                   trees_out.ctypes.data_as(ctypes.c_char_p))
     assert rc == 0
     values, levels, lo, to = [], [], 0, 0
