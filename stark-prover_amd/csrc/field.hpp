@@ -58,6 +58,16 @@ FRI_HD uint32_t neg(uint32_t a) { return a ? P - a : 0u; }
 FRI_HD uint32_t to_mont(uint32_t a) { return mmul(a, R2_MOD_P); }
 FRI_HD uint32_t from_mont(uint32_t a) { return redc((uint64_t)a); }
 
+// One FRI fold (src/fri/fri_commit.rs:53-65): L'[i] = 2^-1 * ((a + b) +
+// beta * (a - b) * x_i^-1), a = L[i], b = L[i + m/2] = L(-x_i); xinv_m =
+// Montgomery(x_i^-1), beta_m = Montgomery(beta), canonical in and out.
+constexpr uint32_t INV2_M = 0x80000000u;     // Montgomery(2^-1) = 2^31 mod p
+static_assert(((unsigned __int128)INV2_M * 2) % P == R_MOD_P, "INV2_M");
+FRI_HD uint32_t fold_one(uint32_t a, uint32_t b, uint32_t xinv_m, uint32_t beta_m) {
+    const uint32_t s = add(a, b), t = sub(a, b);
+    return mmul(add(s, mmul(mmul(t, xinv_m), beta_m)), INV2_M);
+}
+
 // Montgomery-domain power: base_m in Montgomery form, result Montgomery form.
 FRI_HD uint32_t mpow(uint32_t base_m, uint64_t e) {
     uint32_t r = R_MOD_P;   // 1 in Montgomery form

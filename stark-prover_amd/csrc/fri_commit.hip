@@ -165,7 +165,6 @@ static void enqueue_commit(fri_ctx* ctx) {
     NttPlan np = lde_plan(ctx, log_n);
     np.pre_lo = p.pre_lo;
     np.pre_hi = p.pre_hi;
-    np.scratch = p.trees;                 // free until layer 0's leaf kernel (>= 16n words)
     size_t sp = span_begin(ctx, "lde", p.d * 4 + n * 4);
     launch_ntt(np, p.src, p.d, p.layers + p.layer_off[0], s);
     span_end(ctx, sp);

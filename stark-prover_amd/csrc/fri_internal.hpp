@@ -12,10 +12,7 @@ namespace fri {
 
 constexpr int MAXR = 32;            // == FRI_MAX_ROUNDS
 constexpr uint32_t TOP_LOG = 9;         // single-workgroup tree top: <= 512 inputs
-#ifndef FRI_TAIL_LOG
-#define FRI_TAIL_LOG 9
-#endif
-constexpr uint32_t TAIL_LOG = FRI_TAIL_LOG;   // layers of <= 2^TAIL_LOG elements run in the fused tail
+constexpr uint32_t TAIL_LOG = TOP_LOG;  // layers of <= 2^TAIL_LOG elements run in the fused tail
 constexpr uint32_t POW_LO_LOG = 12;     // two-level power tables s^j = lo[j&4095]*hi[j>>12]
 
 // Device-resident commit state (one per context).  Every per-round kernel
@@ -61,7 +58,6 @@ struct NttPlan {
     const uint32_t* pre_hi;
     const uint32_t* post_lo;     // optional output scale t^j (Montgomery, two-level)
     const uint32_t* post_hi;
-    uint32_t* scratch;           // optional 2^log_n words the transform may use (2^24 coset LDE); else nullptr
     // Batch (the product tree's levels, fri_roots.hip): 0 or 1 is one
     // transform; else `batch` transforms in the same launches (grid y),
     // transform b reading src + b*src_stride (d words each) and writing

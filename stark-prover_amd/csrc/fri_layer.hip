@@ -1,79 +1,50 @@
 // fri_layer.hip — per-layer FRI commit pipeline on gfx950.
 //
-// One FRI layer k (2^L evaluations) is committed by at most three kinds of
-// launch, all gated on the device state (no host round trip per round):
+// One FRI layer k (2^L evaluations, L >= 10) is committed by a leaf launch,
+// mid launches and a top launch, all gated on the device state (no host round
+// trip per round); the schedule is at launch_layer:
 //
-//   k_layer_leaf  (2^(L-10) workgroups, L >= 11)
+//   k_layer_leaf  (2^(L-11) workgroups, L >= 19), k_layer_leaf_wide (L < 19)
 //       fold of layer k-1 with beta_{k-1}      (src/fri/fri_commit.rs:53-65)
 //       leaf hashes SHA256(u64_be(v))           (src/merkle/mod.rs:14-15)
-//       tree levels 1..4 (2048 leaves -> 128 nodes per workgroup)
+//       tree levels 1..4 (2048 leaves -> 128 nodes per workgroup), wide: 1..8
 //       a slice of the coefficient fold of round k-1 (fri_commit.rs:32-50)
 //       with per-workgroup maxima (no hot atomics) for the exact degree
 //   k_tree_mid    (levels l -> l+4, 1024 nodes in / 64 out per workgroup)
-//   k_tree_top    (ONE workgroup): last <= 10 levels -> root, degree of
+//   k_tree_mid8   (levels l -> l+8, 256 nodes in / 1 out per workgroup)
+//   k_tree_top    (ONE workgroup): last <= 9 levels -> root, degree of
 //       poly_k, Fiat-Shamir step (channel.rs:35-55): send(root_hex),
 //       beta_k = U256(state) mod p or the final send (fri_commit.rs:114).
-//       For layers of <= 2^10 elements it also does the fold, the leaves and
-//       the whole coefficient fold itself (single launch per small layer).
+//   k_tree_tail   (ONE workgroup, ONE launch): all of a commit's layers of
+//       <= 2^9 elements, each one whole (fold, leaves, levels, coefficient
+//       fold, channel step).
 //
-// Each thread of the leaf / mid kernels takes 4 consecutive inputs and folds
-// them to one level+2 node in registers (no LDS, no barrier, no idle lanes);
-// levels +3/+4 pair through LDS.  Loads/stores of values are 16 B per lane.
+// Each thread of k_layer_leaf takes 4 consecutive leaves and folds them to one
+// level-2 node in registers (no LDS, no barrier, no idle lanes); levels 3 / 4
+// pair through LDS.  Its loads / stores of values are 16 B per lane.
+#include <cassert>
 #include "fri_internal.hpp"
 #include "sha256_fast.hpp"
 #include "sha256_quad.hpp"
 
 namespace fri {
 
-constexpr uint32_t INV2_M2 = 0x80000000u;   // Montgomery(2^-1) = 2^31 mod p
-
-// Diagnostic build (-DFRI_STAMPS, lib/libfri_amd_stamps.so): thread 0 of a
-// top kernel records s_memrealtime at phase boundaries.  Never in the product.
+// Diagnostic build (-DFRI_STAMPS, lib/libfri_amd_stamps.so): where `on`
+// holds, a lane records s_memrealtime (STAMP) or s_memtime (STAMP_CLK) into
+// slot i of its layer's row (t: the layer's LayerTask, commit mode).  The
+// kernels differ only in `on`: lane 0 (or lane 448, the channel wave) of a
+// commit's top or tail, lane 0 of workgroup 0 of a wide leaf kernel (slots
+// 60..62: start, leaves done, levels done).  Never in the product.
 #ifdef FRI_STAMPS
-#define TOP_STAMP(i)                                                                     \
-    do {                                                                                 \
-        if (COMMIT && threadIdx.x == 0) t.st->stamps[t.k][(i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#define TOP_CLK(i)                                                                               \
-    do {                                                                                           \
-        if (COMMIT && threadIdx.x == 0) t.st->stamps[t.k][(i)] = __builtin_amdgcn_s_memtime();     \
-    } while (0)
-#define TOP_STAMP_T(i, tid_)                                                                       \
-    do {                                                                                           \
-        if (COMMIT && threadIdx.x == (tid_)) t.st->stamps[t.k][(i)] = __builtin_amdgcn_s_memrealtime(); \
+#define STAMP_WITH(on, i, fn)                                  \
+    do {                                                       \
+        if (on) t.st->stamps[t.k][(i)] = fn();                 \
     } while (0)
 #else
-#define TOP_STAMP(i) do {} while (0)
-#define TOP_CLK(i) do {} while (0)
-#define TOP_STAMP_T(i, tid_) do {} while (0)
+#define STAMP_WITH(on, i, fn) do {} while (0)
 #endif
-// workgroup 0 of a wide leaf kernel: start, leaves done, levels done (60..62)
-#ifdef FRI_STAMPS
-#define WIDE_STAMP(i)                                                                              \
-    do {                                                                                           \
-        if (COMMIT && blockIdx.x == 0 && threadIdx.x == 0) t.st->stamps[t.k][(i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define WIDE_STAMP(i) do {} while (0)
-#endif
-// the same marks for a layer of the tail kernel (t: that layer's task)
-#ifdef FRI_STAMPS
-#define TAIL_STAMP_T(i, tid_, fn)                                                  \
-    do {                                                                           \
-        if (threadIdx.x == (tid_)) t.st->stamps[t.k][(i)] = fn();                  \
-    } while (0)
-#define TAIL_STAMP(i) TAIL_STAMP_T(i, 0, __builtin_amdgcn_s_memrealtime)
-#define TAIL_CLK(i) TAIL_STAMP_T(i, 0, __builtin_amdgcn_s_memtime)
-#else
-#define TAIL_STAMP_T(i, tid_, fn) do {} while (0)
-#define TAIL_STAMP(i) do {} while (0)
-#define TAIL_CLK(i) do {} while (0)
-#endif
-
-__device__ __forceinline__ uint32_t fold1(uint32_t a, uint32_t b, uint32_t xinv_m, uint32_t beta_m) {
-    uint32_t s = add(a, b), t = sub(a, b);
-    return mmul(add(s, mmul(mmul(t, xinv_m), beta_m)), INV2_M2);
-}
+#define STAMP(on, i) STAMP_WITH(on, i, __builtin_amdgcn_s_memrealtime)
+#define STAMP_CLK(on, i) STAMP_WITH(on, i, __builtin_amdgcn_s_memtime)
 
 // Wave priority of the latency-bound chain kernels (tops, tail, narrow mids):
 // s_setprio raises their waves over co-resident throughput waves (another
@@ -144,12 +115,6 @@ __device__ __forceinline__ void pair_level(const uint4* A, uint4* B, uint32_t* o
 #ifndef FRI_SCHED_PRODUCER
 #define FRI_SCHED_PRODUCER 1
 #endif
-// The channel's root blocks (jobs 3, 4) with their schedule on wave 6
-// (chan_produce): within noise, 4.612 vs 4.616 ms per 2^24 commit over 4
-// interleaved A/B rounds (profiles/r05_sched_channel_ab.txt), so off.
-#ifndef FRI_SCHED_CHANNEL
-#define FRI_SCHED_CHANNEL 0
-#endif
 struct SchedLds {
     uint32_t wk[32 * 48];       // per node W16..W63 + K (16-byte aligned rows of 48 words)
     uint32_t flag;
@@ -199,6 +164,38 @@ __device__ __forceinline__ int wave_max_i(int v) {
     return v;
 }
 
+// The three maxima of a coefficient task, -1 where there is none.  Round
+// k >= 1: the largest j with c'_j != 0, with c_2j != 0, with c_2j+1 != 0.
+// k == 0: m0 = the largest index of a nonzero input coefficient, m1 >= 0
+// flags a coefficient >= p, m2 unused.
+struct Mx3 {
+    int m0 = -1, m1 = -1, m2 = -1;
+    // triple i of an array of triples
+    __device__ __forceinline__ void load(const int32_t* p, uint32_t i) { m0 = p[3 * i]; m1 = p[3 * i + 1]; m2 = p[3 * i + 2]; }
+    __device__ __forceinline__ void take(const int32_t* p, uint32_t i) {
+        m0 = max(m0, p[3 * i]); m1 = max(m1, p[3 * i + 1]); m2 = max(m2, p[3 * i + 2]);
+    }
+    __device__ __forceinline__ void store(int32_t* p, uint32_t i) const { p[3 * i] = m0; p[3 * i + 1] = m1; p[3 * i + 2] = m2; }
+    __device__ __forceinline__ void wave_max() { m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2); }
+};
+// The wave's maxima into red[3 * wave ..] (tx: the thread's index among the
+// whole waves that take part); then, after a barrier, the nw waves' triples.
+__device__ __forceinline__ void mx3_wave_to_red(Mx3 m, int32_t* red, uint32_t tx) {
+    m.wave_max();
+    if ((tx & 63) == 0) m.store(red, tx >> 6);
+}
+__device__ __forceinline__ Mx3 mx3_from_red(const int32_t* red, uint32_t nw) {
+    Mx3 m;
+    for (uint32_t i = 0; i < nw; i++) m.take(red, i);
+    return m;
+}
+// Degree of poly_k (reference degree field; see DevState) from the layer's
+// maxima; noncanon: an input coefficient >= p (layer 0 only, FRI_EINVAL).
+struct Degree { int deg; bool noncanon; };
+__device__ __forceinline__ Degree degree_of(int k, const Mx3& m) {
+    return {k == 0 ? m.m0 : (m.m1 < 0 ? m.m2 : m.m0), k == 0 && m.m1 >= 0};
+}
+
 // Coefficient task of one workgroup (w of G): k == 0 -> max nonzero index
 // of the input (deg_0); k >= 1 -> fold slice c'_j = c_2j + beta c_2j+1 with
 // maxima of c', even part, odd part.  Results: wgmax[3w .. 3w+2].
@@ -207,21 +204,21 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // barrier): red -> wgmax.
 __device__ __forceinline__ void coef_slice(const LayerTask& t, uint32_t w, uint32_t G, int32_t* red, uint32_t t0,
                                            uint32_t nthr) {
-    int m0 = -1, m1 = -1, m2 = -1;
+    Mx3 m;
     const uint32_t tx = threadIdx.x - t0;
     // this rank's coefficient range (all of poly_k unless sharded), split
     // evenly over the G workgroups; indices j are global
     const size_t jhi_all = t.jhi ? t.jhi : ~(size_t)0;
     if (t.k == 0) {
-        // m1 >= 0 flags a coefficient >= p (the input is validated here, on
-        // the device, instead of by a host scan before the upload)
+        // (the input is validated here, on the device, instead of by a host
+        // scan before the upload)
         const size_t a = t.jlo, b = min(t.d0, jhi_all), n = b > a ? b - a : 0;
         const size_t cs = (n + G - 1) / G, lo = a + (size_t)w * cs, hi = min(b, lo + cs);
         const uint32_t* in = t.coef_in - t.ibase;
         for (size_t j = lo + tx; j < hi; j += nthr) {
             const uint32_t c = in[j];
-            if (c) m0 = max(m0, (int)j);
-            if (c >= P) m1 = 0;
+            if (c) m.m0 = max(m.m0, (int)j);
+            if (c >= P) m.m1 = 0;
         }
     } else {
         const DevState* st = t.st;
@@ -236,19 +233,15 @@ __device__ __forceinline__ void coef_slice(const LayerTask& t, uint32_t w, uint3
             uint32_t o = (2 * j + 1 < len) ? in[2 * j + 1] : 0u;
             uint32_t v = add(e, mmul(o, beta_m));
             outp[j] = v;
-            if (v) m0 = (int)j;
-            if (e) m1 = (int)j;
-            if (o) m2 = (int)j;
+            if (v) m.m0 = (int)j;
+            if (e) m.m1 = (int)j;
+            if (o) m.m2 = (int)j;
         }
     }
-    m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2);
-    const uint32_t wave = tx >> 6;
-    if ((tx & 63) == 0) { red[3 * wave] = m0; red[3 * wave + 1] = m1; red[3 * wave + 2] = m2; }
+    mx3_wave_to_red(m, red, tx);
 }
 __device__ __forceinline__ void coef_combine(const LayerTask& t, uint32_t w, const int32_t* red, uint32_t nw) {
-    int a = -1, b = -1, c = -1;
-    for (uint32_t i = 0; i < nw; i++) { a = max(a, red[3 * i]); b = max(b, red[3 * i + 1]); c = max(c, red[3 * i + 2]); }
-    t.wgmax[3 * w] = a; t.wgmax[3 * w + 1] = b; t.wgmax[3 * w + 2] = c;
+    mx3_from_red(red, nw).store(t.wgmax, w);
 }
 __device__ __forceinline__ void coef_task(const LayerTask& t, uint32_t w, uint32_t G, int32_t* red /*LDS [3*waves]*/) {
     coef_slice(t, w, G, red, 0, blockDim.x);
@@ -256,40 +249,19 @@ __device__ __forceinline__ void coef_task(const LayerTask& t, uint32_t w, uint32
     if (threadIdx.x == 0) coef_combine(t, w, red, blockDim.x / 64);
 }
 
-#ifndef FRI_QUAD_LEAVES_FIRST
-#define FRI_QUAD_LEAVES_FIRST 1
-#endif
-// Four consecutive level-l digests (or leaves) per thread -> level l+2 node.
-// lv0/lv1 are this layer's level l+0 / l+1 arrays (lv0 written only for
-// leaves: it is the input otherwise).
-template <bool LEAVES>
-__device__ __forceinline__ void quad(const uint4& vals, const uint32_t* in0, uint32_t* lv0, uint32_t* lv1,
-                                     size_t q /*quad index*/, Dg& out) {
-    Dg a, b, n0, n1;
-#if FRI_QUAD_LEAVES_FIRST
-    if (LEAVES) {
-        // all four leaves first: the thread's 128 contiguous level-l bytes are
-        // written together (no partly written line waits in L2 for its other
-        // half), and so are its two level-(l+1) digests
-        Dg c, d;
-        hleaf(vals.x, a); hleaf(vals.y, b); hleaf(vals.z, c); hleaf(vals.w, d);
-        dg_store(lv0 + 8 * (4 * q), a); dg_store(lv0 + 8 * (4 * q + 1), b);
-        dg_store(lv0 + 8 * (4 * q + 2), c); dg_store(lv0 + 8 * (4 * q + 3), d);
-        hnode(a, b, n0);
-        hnode(c, d, n1);
-        dg_store(lv1 + 8 * (2 * q), n0);
-        dg_store(lv1 + 8 * (2 * q + 1), n1);
-        hnode(n0, n1, out);
-        return;
-    }
-#endif
-    if (LEAVES) { hleaf(vals.x, a); hleaf(vals.y, b); dg_store(lv0 + 8 * (4 * q), a); dg_store(lv0 + 8 * (4 * q + 1), b); }
-    else { dg_load(in0 + 8 * (4 * q), a); dg_load(in0 + 8 * (4 * q + 1), b); }
+// Four consecutive leaves per thread -> level 2 node; lv0 / lv1 are the
+// layer's level 0 / 1 arrays.  All four leaves first: the thread's 128
+// contiguous level-0 bytes are written together (no partly written line waits
+// in L2 for its other half), and so are its two level-1 digests.
+__device__ __forceinline__ void quad(const uint4& vals, uint32_t* lv0, uint32_t* lv1, size_t q /*quad index*/,
+                                     Dg& out) {
+    Dg a, b, c, d, n0, n1;
+    hleaf(vals.x, a); hleaf(vals.y, b); hleaf(vals.z, c); hleaf(vals.w, d);
+    dg_store(lv0 + 8 * (4 * q), a); dg_store(lv0 + 8 * (4 * q + 1), b);
+    dg_store(lv0 + 8 * (4 * q + 2), c); dg_store(lv0 + 8 * (4 * q + 3), d);
     hnode(a, b, n0);
+    hnode(c, d, n1);
     dg_store(lv1 + 8 * (2 * q), n0);
-    if (LEAVES) { hleaf(vals.z, a); hleaf(vals.w, b); dg_store(lv0 + 8 * (4 * q + 2), a); dg_store(lv0 + 8 * (4 * q + 3), b); }
-    else { dg_load(in0 + 8 * (4 * q + 2), a); dg_load(in0 + 8 * (4 * q + 3), b); }
-    hnode(a, b, n1);
     dg_store(lv1 + 8 * (2 * q + 1), n1);
     hnode(n0, n1, out);
 }
@@ -344,15 +316,15 @@ __global__ __launch_bounds__(TPB) void k_layer_leaf(LayerTask t) {
         uint4 a = reinterpret_cast<const uint4*>(t.prev)[q];
         uint4 b = reinterpret_cast<const uint4*>(PAIR ? t.prev2 : t.prev + half)[q];
         uint4 x = reinterpret_cast<const uint4*>(t.xinv)[q];
-        v.x = fold1(a.x, b.x, x.x, beta_m); v.y = fold1(a.y, b.y, x.y, beta_m);
-        v.z = fold1(a.z, b.z, x.z, beta_m); v.w = fold1(a.w, b.w, x.w, beta_m);
+        v.x = fold_one(a.x, b.x, x.x, beta_m); v.y = fold_one(a.y, b.y, x.y, beta_m);
+        v.z = fold_one(a.z, b.z, x.z, beta_m); v.w = fold_one(a.w, b.w, x.w, beta_m);
         reinterpret_cast<uint4*>(t.values)[q] = v;
     } else {
         v = reinterpret_cast<const uint4*>(t.values)[q];
     }
     uint32_t* tr = t.tree;
     Dg top;
-    quad<true>(v, nullptr, tr + 8 * level_offset(L, 0), tr + 8 * level_offset(L, 1), q, top);
+    quad(v, tr + 8 * level_offset(L, 0), tr + 8 * level_offset(L, 1), q, top);
     if (COMMIT) coef_task(t, blockIdx.x, gridDim.x, red);
     lds_two_levels<TPB>(lds, top, tr + 8 * level_offset(L, 2), tr + 8 * level_offset(L, 3),
                         tr + 8 * level_offset(L, 4), wg * TPB);
@@ -374,7 +346,7 @@ __host__ __device__ __forceinline__ uint32_t wide_levels(uint32_t L) { return L 
 template <bool FOLD, bool COMMIT, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_layer_leaf_wide(LayerTask t) {
     if (gated_off(t)) return;
-    WIDE_STAMP(60);
+    STAMP(COMMIT && blockIdx.x == 0 && threadIdx.x == 0, 60);
     __shared__ uint4 lds[2 * 256 + 2 * 128];
     __shared__ int32_t red[12];
     __shared__ SchedLds sl;
@@ -387,7 +359,7 @@ __global__ __launch_bounds__(256) void k_layer_leaf_wide(LayerTask t) {
     if (FOLD) {
         const size_t half = (size_t)1 << L;
         const uint32_t beta_m = COMMIT ? t.st->beta_mont[t.k - 1] : (PAIR ? pair_beta(t) : t.beta_m);
-        v = fold1(t.prev[i], PAIR ? t.prev2[i] : t.prev[i + half], t.xinv[i], beta_m);
+        v = fold_one(t.prev[i], PAIR ? t.prev2[i] : t.prev[i + half], t.xinv[i], beta_m);
         t.values[i] = v;
     } else {
         v = t.values[i];
@@ -400,7 +372,7 @@ __global__ __launch_bounds__(256) void k_layer_leaf_wide(LayerTask t) {
     uint4* B = lds + 2 * 256;
     dg_lds_store(A + 2 * threadIdx.x, d);
     lds_barrier();
-    WIDE_STAMP(61);
+    STAMP(COMMIT && blockIdx.x == 0 && threadIdx.x == 0, 61);
     uint32_t cnt = 256;
     const shaq::Role qr = shaq::role_of(threadIdx.x);
     if (grid * 128 < WIDE_PAIR_MAX) chain_prio();   // from level 1 on, all on lane pairs
@@ -426,35 +398,28 @@ __global__ __launch_bounds__(256) void k_layer_leaf_wide(LayerTask t) {
         uint4* tmp = A; A = B; B = tmp;
     }
     if (COMMIT && threadIdx.x == 128) coef_combine(t, blockIdx.x, red, 2);   // nlev >= 4: red[] settled
-    WIDE_STAMP(62);
+    STAMP(COMMIT && blockIdx.x == 0 && threadIdx.x == 0, 62);
 }
 
 // Reduce the coefficient-maxima triples of the R producer workgroups of this
 // workgroup's inputs (R <= 64) into one triple (wave 0).
 __device__ __forceinline__ void reduce_mx(const int32_t* in, int32_t* out, uint32_t w, uint32_t R) {
     if (threadIdx.x >= 64) return;
-    const uint32_t i = R * w + threadIdx.x;
-    int a = -1, b = -1, c = -1;
-    if (threadIdx.x < R) { a = in[3 * i]; b = in[3 * i + 1]; c = in[3 * i + 2]; }
-    a = wave_max_i(a); b = wave_max_i(b); c = wave_max_i(c);
-    if (threadIdx.x == 0) { out[3 * w] = a; out[3 * w + 1] = b; out[3 * w + 2] = c; }
+    Mx3 m;
+    if (threadIdx.x < R) m.load(in, R * w + threadIdx.x);
+    m.wave_max();
+    if (threadIdx.x == 0) m.store(out, w);
 }
 
-#ifndef MID_PAIR_BY_WG
-#define MID_PAIR_BY_WG 0     // 1: k_tree_mid<1024> levels 2-4 on lane pairs whatever the layer width (round-2 form)
-#endif
-
-// Mid tree: NIN level-l nodes per workgroup -> NIN/16 level-(l+4) nodes,
-// one node per lane per level.  NIN = 1024 (512 threads) for wide levels,
-// 256 (128 threads: one wave per SIMD on every level) for narrow ones.
-template <uint32_t NIN>
-__global__ __launch_bounds__(NIN / 2) void k_tree_mid(uint32_t* tree, uint32_t L, uint32_t l, const DevState* st,
-                                                      int gate, const int32_t* mx_in, int32_t* mx_out, uint32_t R) {
+// Mid tree of the wide levels: NIN = 1024 level-l nodes per workgroup (512
+// threads) -> 64 level-(l+4) nodes, one node per lane per level.
+__global__ __launch_bounds__(512) void k_tree_mid(uint32_t* tree, uint32_t L, uint32_t l, const DevState* st,
+                                                  int gate, const int32_t* mx_in, int32_t* mx_out, uint32_t R) {
     if (st && gate >= 0 && !st->active[gate]) return;
-    if (NIN == 256) chain_prio();
+    constexpr uint32_t NIN = 1024;
     // level 1 reads its two inputs straight from HBM (64 contiguous bytes per
     // thread), so LDS holds only levels 1.. (NIN/2 + NIN/4 digests): more
-    // workgroups per CU for the wide instance
+    // workgroups per CU
     __shared__ uint4 lds[NIN + NIN / 2];
     __shared__ SchedLds sl;
     sched_init(&sl);
@@ -481,9 +446,8 @@ __global__ __launch_bounds__(NIN / 2) void k_tree_mid(uint32_t* tree, uint32_t L
         uint32_t* out = tree + 8 * (level_offset(L, l + j) + (base >> j));
         // lane pairs only where the whole level is narrow: a lane-pair node
         // issues 1744 instructions on two lanes, a per-lane node 2290 on one,
-        // and the wide instance's levels of >= 2^16 nodes are issue-bound
-        const bool narrow = NIN == 1024 && !MID_PAIR_BY_WG ? (size_t)cnt * gridDim.x < WIDE_PAIR_MAX
-                                                           : 2 * cnt <= NIN / 2;
+        // and levels of >= 2^16 nodes are issue-bound
+        const bool narrow = (size_t)cnt * gridDim.x < WIDE_PAIR_MAX;
         if (narrow) {
             pair_level_s(A, B, out, t, cnt, qr, &sl, j);   // narrow: latency-bound
         } else if (t < cnt) {
@@ -501,8 +465,8 @@ __global__ __launch_bounds__(NIN / 2) void k_tree_mid(uint32_t* tree, uint32_t L
 
 // Eight tree levels in one launch for the narrow part of a large layer:
 // 256 level-l digests per workgroup -> 1 level-(l+8) digest, every level on
-// lane pairs (level 1 reads its children straight from HBM).  Replaces two
-// k_tree_mid<256> launches: one kernel boundary, one HBM round trip of the
+// lane pairs (level 1 reads its children straight from HBM).  Against two
+// four-level launches: one kernel boundary, one HBM round trip of the
 // level-(l+4) digests and one cold start less per layer.
 __global__ __launch_bounds__(256) void k_tree_mid8(uint32_t* tree, uint32_t L, uint32_t l, const DevState* st,
                                                    int gate, const int32_t* mx_in, int32_t* mx_out, uint32_t R) {
@@ -596,12 +560,8 @@ enum { CJ_REHASH = 0, CJ_MID = 2, CJ_ROOT = 3, CJ_FINAL = 6, CJ_END_ROUND = 6, C
 
 // Lane-pair form (sha256_quad.hpp): X is this lane's half of the chaining
 // value (even lane words 4..7, odd lane 0..3); cs stays whole on every lane.
-// wk (FRI_SCHED_PRODUCER): the two root-message blocks (jobs 3, 4) take their
-// rounds 16..63 from rows 0 / 1 of wk, made by chan_produce on wave 6; flags
-// base + 1 .. base + 6.
 __device__ __forceinline__ void chan_job(int j, uint32_t cs[8], uint32_t X[4], uint32_t has, const uint4* root_lds,
-                                         uint32_t fv, const shaq::Role& R, const uint32_t* wk = nullptr,
-                                         const uint32_t* flag = nullptr, uint32_t base = 0) {
+                                         uint32_t fv, const shaq::Role& R) {
     // the job and the channel flags are wave-uniform: in SGPRs the job's
     // branches are scalar and its padding table is read by scalar loads
     // (a per-lane table pointer costs a vector-load round trip per 16 rounds)
@@ -636,7 +596,6 @@ __device__ __forceinline__ void chan_job(int j, uint32_t cs[8], uint32_t X[4], u
         w[15] = 80u * 8u;                           // hex(state) (64) + 16 chars
     }
     if (pad) shaq::compress_kw(X, j == 1 ? shaf::PAD_KW_C.kw : (has ? shaf::PAD_KW_1536.kw : shaf::PAD_KW_1024.kw), R);
-    else if (wk && (j == 3 || j == 4)) shaq::compress_ext(X, w, R, wk + 48 * (j - 3), flag, base + 3 * (j - 3));
     else shaq::compress(X, w, R);
     if (j == 1 || j == 5 || j == 7) {            // cs = X, both halves on every lane
 #pragma unroll
@@ -645,24 +604,6 @@ __device__ __forceinline__ void chan_job(int j, uint32_t cs[8], uint32_t X[4], u
             cs[i] = R.is_a ? X[i] : o;
             cs[4 + i] = R.is_a ? o : X[i];
         }
-    }
-}
-
-// The schedules of the root message's two blocks (jobs 3 and 4: hex(hex(root))
-// in two 64-byte halves), on a producer wave while the channel wave runs the
-// rounds: both messages are known once the root is, so the producer makes
-// both rows (0, 1) in the iteration of job 3; flags base + 1 .. base + 6.
-__device__ __forceinline__ void chan_produce(const uint4* root_lds, SchedLds* sl, uint32_t base, const shaq::Role& R) {
-    const uint32_t lane = __lane_id();
-#pragma unroll 1
-    for (uint32_t jb = 0; jb < 2; jb++) {
-        const uint32_t b = (lane & 15u) + 16u * jb;
-        const uint32_t rw = reinterpret_cast<const uint32_t*>(root_lds)[b >> 2];
-        const uint32_t hh = hexhex((rw >> (24 - 8 * (b & 3))) & 255u);
-        uint32_t w[16];
-#pragma unroll
-        for (int jj = 0; jj < 16; jj++) w[jj] = __builtin_amdgcn_readlane(hh, jj);
-        shaq::produce(w, sl->wk + 48 * jb, &sl->flag, base + 3 * jb, lane == 0, lane == 0, R);
     }
 }
 
@@ -684,14 +625,133 @@ __device__ __forceinline__ uint32_t chan_beta(const uint32_t s[8]) {
     return add(add(add(t[0], t[1]), add(t[2], t[3])), add(add(t[4], t[5]), add(t[6], t[7])));
 }
 
+// --------------------------------------------- shared by top and tail ----
+// What k_tree_top and k_tree_tail (one workgroup of 512 threads each, wave 7
+// the channel wave) both do, written once.  Everything here is inlined: the
+// two kernels keep their own LDS footprints and register budgets.
+
+// The leaves of a layer of N <= 512 values: value(j, real) yields layer
+// value j (and stores what its kernel keeps of it); leaf digests to the
+// tree's level 0 and to A.  Under 64 leaves the spare lanes of wave 0 hash
+// leaf (i mod N) and store nothing: a partly masked wave is slower (see
+// pair_level).
+template <typename Value>
+__device__ __forceinline__ void leaf_loop(uint32_t N, uint32_t* tr, uint4* A, Value&& value) {
+    for (uint32_t i = threadIdx.x; i < max(N, 64u); i += blockDim.x) {
+        const uint32_t j = i & (N - 1);          // N is a power of two
+        const bool real = i < N;
+        const uint32_t v = value(j, real);
+        Dg d;
+        cleaf(v, d);
+        if (real) {
+            dg_store(tr + 8 * j, d);
+            dg_lds_store(A + 2 * j, d);
+        }
+    }
+}
+
+// One tree level: cnt nodes from A into B and `out`.  ord: see pair_level_s.
+// (stamps, FRI_STAMPS builds: slots 24 + 2 it / 25 + 2 it around the first node)
+__device__ __forceinline__ void level_step(const LayerTask& t, bool stamps, uint32_t it, const uint4* A, uint4* B,
+                                           uint32_t* out, uint32_t cnt, const shaq::Role& R, SchedLds* sl,
+                                           uint32_t ord) {
+    const uint32_t tid = threadIdx.x;
+    if (cnt <= 128) {                   // waves 0-3, one per SIMD (wave 7: channel)
+        STAMP_CLK(stamps && it < 18 && tid == 0, 24 + 2 * it);
+        pair_level_s(A, B, out, tid, cnt, R, sl, ord);
+        STAMP_CLK(stamps && it < 18 && tid == 0, 25 + 2 * it);
+        return;
+    }
+#pragma unroll 1
+    for (uint32_t q = tid; q < cnt; q += blockDim.x) {
+        Dg a, b, o;
+        dg_lds_load(A + 4 * q, a);
+        dg_lds_load(A + 4 * q + 2, b);
+#ifdef FRI_STAMPS
+        if (stamps && it < 18 && q == 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
+        STAMP_CLK(stamps && it < 18 && q == 0, 24 + 2 * it);
+        cnode(a, b, o);
+        STAMP_CLK(stamps && it < 18 && q == 0, 25 + 2 * it);
+        dg_lds_store(B + 2 * q, o);
+        dg_store(out + 8 * q, o);
+    }
+}
+
+// The channel wave's jobs of one iteration of the level loop: during a narrow
+// level (SIMD 3 idle) one pre-root job, after the last level every job still
+// left.  Its kernel's ONE chan_job call site (see chan_job).
+__device__ __forceinline__ int chan_drain(const LayerTask& t, int job, int job_end, bool level, uint32_t cnt,
+                                           uint32_t cs[8], uint32_t X[4], uint32_t has, const uint4* root_lds,
+                                           uint32_t fv, const shaq::Role& R) {
+    if (job >= job_end || (level && !(cnt <= 192 && job < CJ_ROOT))) return job;
+    do {
+        STAMP(threadIdx.x == 448 && job == CJ_ROOT, 14);           // job 3 / job 5 start (14, 13)
+        STAMP(threadIdx.x == 448 && job == CJ_ROOT + 2, 13);
+        chan_job(job, cs, X, has, root_lds, fv, R);
+        STAMP(threadIdx.x == 448 && job >= CJ_ROOT && job <= CJ_ROOT + 2, 20 + job - CJ_ROOT);   // done (20..22)
+        job++;
+    } while (!level && job < job_end);
+    return job;
+}
+
+// Results of layer t.k, by one lane of the channel wave after its last job:
+// DevState's record of the layer and either the Fiat-Shamir step (round:
+// beta_k, channel.rs:35-55), the final send (fri_commit.rs:114) or an error
+// (FRI_EINVAL, FRI_EDEGREE).  cs: the channel state after the layer's sends;
+// fbeta1: the test hook's beta + 1, or 0 when beta is not forced; root_lds:
+// the tree's root.  Returns what a next layer in the same launch needs.
+struct RoundOut { uint32_t active, beta_m; };
+__device__ __forceinline__ RoundOut layer_results(const LayerTask& t, const Degree& dg, const uint32_t cs[8],
+                                                  uint32_t fv, uint32_t fbeta1, const uint4* root_lds) {
+    DevState* st = t.st;
+    const int k = t.k, deg = dg.deg;
+    if (dg.noncanon) {                             // FRI_EINVAL: nothing of this commit is served
+        st->active[k] = 0;
+        st->status = 1u;
+        return {0u, 0u};
+    }
+    st->deg[k] = deg;
+    Dg root;
+    dg_lds_load(root_lds, root);
+#pragma unroll
+    for (int i = 0; i < 8; i++) st->roots[k][i] = root.w[i];
+    st->n_layers = (uint32_t)k + 1;
+    STAMP(true, 15);
+    if (deg >= 1 && k < MAXR && t.L >= 1) {
+        uint32_t beta = chan_beta(cs);
+#pragma unroll
+        for (int i = 0; i < 8; i++) st->chan[i] = cs[i];
+        st->chan_has = 1;
+        st->chan_pending = 1;                        // receive's rehash deferred to the next layer's jobs
+        if (fbeta1) beta = fbeta1 - 1u;
+        st->beta[k] = beta;
+        const uint32_t bm = to_mont(beta);
+        st->beta_mont[k] = bm;
+        st->active[k] = 1;
+        st->n_rounds = (uint32_t)k + 1;
+        STAMP(true, 16);
+        return {1u, bm};
+    }
+    st->active[k] = 0;
+    if (deg >= 1) { st->status = 7u; return {0u, 0u}; }       // FRI_EDEGREE
+#pragma unroll
+    for (int i = 0; i < 8; i++) st->chan[i] = cs[i];          // after send(final.to_bytes())
+    st->final_value = fv;
+    st->final_degree = deg;
+    st->chan_has = 1;
+    st->chan_pending = 0;
+    return {0u, 0u};
+}
+
 // ---------------------------------------------------------------- top ----
-// One workgroup.  FROM_LEAVES: the layer has N = 2^L <= 1024 elements and is
-// done entirely here (fold, leaves, all levels, whole coefficient task).
-// Otherwise: N = 2^(L-l) <= 1024 level-l digests -> root.
+// One workgroup.  FROM_LEAVES (a standalone tree of N = 2^L <= 2^TOP_LOG
+// values, never COMMIT: a commit's small layers run in k_tree_tail): leaves
+// and all levels here.  Otherwise: N = 2^(L-l) <= 1024 level-l digests -> root.
 // COMMIT: the degree of poly_k is reduced up front (its inputs are complete
 // at launch); wave 7 runs the channel jobs (chan_job) during the levels whose
-// nodes fit waves 0-2, then after the root, in extra iterations of the level
-// loop (uniform barrier count).
+// nodes fit waves 0-2, then after the root, in an extra iteration of the
+// level loop (uniform barrier count).
 // SHARD (coset-sharded layers, run_commit_sharded; never FROM_LEAVES):
 //   !COMMIT: the top of this rank's block tree; it also writes the rank's
 //            per-layer record (t.shard->rec_out: block root, the maxima of
@@ -701,8 +761,9 @@ __device__ __forceinline__ uint32_t chan_beta(const uint32_t s[8]) {
 //            roots in the all-gathered records (rank order, permuted to block
 //            order and stored as the top tree's level 0), the maxima and the
 //            final-value candidate (rank 0's first coefficient) too.
-template <bool FROM_LEAVES, bool FOLD, bool COMMIT, bool SHARD = false>
+template <bool FROM_LEAVES, bool COMMIT, bool SHARD = false>
 __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const int32_t* mx, uint32_t G) {
+    static_assert(!(FROM_LEAVES && (COMMIT || SHARD)), "from the leaves: standalone trees only");
     if (gated_off(t)) return;
     chain_prio();
     __shared__ uint4 lds[2 * 1024 + 2 * 512];
@@ -716,7 +777,7 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
     const bool chan_wave = COMMIT && tid >= 448;
     DevState* st = t.st;
     uint32_t cs[8], X[4];
-    uint32_t has = 0, forced = 0, fbeta = 0;
+    uint32_t has = 0, fbeta1 = 0;
     int job = CJ_END_FINAL;
     if (chan_wave) {
         // every channel field in one round trip: no load waits on another's
@@ -729,8 +790,7 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
         const uint32_t fo = COMMIT ? st->forced : 0u, fb = st->forced_beta[t.k < MAXR ? t.k : 0];
         has = h;
         job = !h ? CJ_ROOT : (pend ? CJ_REHASH : CJ_MID);
-        forced = fo;
-        if (fo && t.k < MAXR) fbeta = fb;
+        if (fo && t.k < MAXR) fbeta1 = fb + 1u;
     }
     // wave 6 pulls the compact-SHA constant tables into the scalar cache
     // while the inputs load (cold misses inside level 1 and the channel otherwise)
@@ -738,30 +798,9 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
     uint4* A = lds;
     uint4* B = lds + 2 * 1024;
     uint32_t* tr = t.tree;
-    TOP_STAMP(0);
+    STAMP(COMMIT && tid == 0, 0);
     if (FROM_LEAVES) {
-        const size_t half = (size_t)1 << L;
-        const uint32_t beta_m = FOLD ? (COMMIT ? st->beta_mont[t.k - 1] : t.beta_m) : 0u;
-        // under 64 leaves the spare lanes of wave 0 hash leaf (i mod N) and
-        // store nothing: a partly masked wave is slower (see pair_level)
-        for (uint32_t i = tid; i < max(N, 64u); i += blockDim.x) {
-            const uint32_t j = i & (N - 1);          // N is a power of two
-            const bool real = i < N;
-            uint32_t v;
-            if (FOLD) {
-                v = fold1(t.prev[j], t.prev[j + half], t.xinv[j], beta_m);
-                if (real) t.values[j] = v;
-            } else {
-                v = t.values[j];
-            }
-            Dg d;
-            cleaf(v, d);
-            if (real) {
-                dg_store(tr + 8 * j, d);
-                dg_lds_store(A + 2 * j, d);
-            }
-        }
-        if (COMMIT) coef_task(t, 0, 1, red);       // per-wave maxima in red[], wgmax[0..2]
+        leaf_loop(N, tr, A, [&](uint32_t j, bool) { return t.values[j]; });
     } else if (SHARD && COMMIT) {
         const ShardTop& sh = *t.shard;
         for (uint32_t i = tid; i < N; i += blockDim.x) {
@@ -770,20 +809,18 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
             dg_lds_store(A + 2 * i, d);
             dg_store(tr + 8 * i, d);               // level 0 of the top tree (decommitment paths)
         }
-        int m0 = -1, m1 = -1, m2 = -1;
+        Mx3 m;
         if (tid < sh.G) {
-            const int32_t* rm = reinterpret_cast<const int32_t*>(sh.recs_in + REC_WORDS * tid + 8);
-            m0 = rm[0]; m1 = rm[1]; m2 = rm[2];
-            if (sh.sched_on) { m0 = sh.sched_deg; m1 = t.k == 0 ? -1 : 0; m2 = -1; }   // loopback rehearsal
+            m.load(reinterpret_cast<const int32_t*>(sh.recs_in + REC_WORDS * tid + 8), 0);
+            if (sh.sched_on) { m.m0 = sh.sched_deg; m.m1 = t.k == 0 ? -1 : 0; m.m2 = -1; }   // loopback rehearsal
         }
-        m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2);
-        if ((tid & 63) == 0) { red[3 * (tid >> 6)] = m0; red[3 * (tid >> 6) + 1] = m1; red[3 * (tid >> 6) + 2] = m2; }
+        mx3_wave_to_red(m, red, tid);
     } else {
         const uint32_t* in = tr + 8 * level_offset(L, l);
         // the producers' maxima are loaded before the digests are waited
         // for: both round trips overlap (G <= 512 triples, one per thread)
-        int p0 = -1, p1 = -1, p2 = -1;
-        if (COMMIT && tid < G) { p0 = mx[3 * tid]; p1 = mx[3 * tid + 1]; p2 = mx[3 * tid + 2]; }
+        Mx3 m;
+        if (COMMIT && tid < G) m.load(mx, tid);
         for (uint32_t i = tid; i < N; i += blockDim.x) {
             Dg d;
             dg_load(in + 8 * i, d);
@@ -791,46 +828,28 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
         }
         if (SHARD && !COMMIT) {                    // this rank's coefficient-slice maxima
             const ShardTop& sh = *t.shard;
-            int m0 = -1, m1 = -1, m2 = -1;
-            for (uint32_t i = tid; i < sh.rec_R; i += blockDim.x) {
-                m0 = max(m0, sh.rec_mx[3 * i]); m1 = max(m1, sh.rec_mx[3 * i + 1]); m2 = max(m2, sh.rec_mx[3 * i + 2]);
-            }
-            m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2);
-            if ((tid & 63) == 0) { red[3 * (tid >> 6)] = m0; red[3 * (tid >> 6) + 1] = m1; red[3 * (tid >> 6) + 2] = m2; }
+            for (uint32_t i = tid; i < sh.rec_R; i += blockDim.x) m.take(sh.rec_mx, i);
+            mx3_wave_to_red(m, red, tid);
         }
         if (COMMIT) {                              // producer maxima -> per-wave triples
-            int m0 = p0, m1 = p1, m2 = p2;
-            for (uint32_t i = tid + blockDim.x; i < G; i += blockDim.x) {
-                m0 = max(m0, mx[3 * i]); m1 = max(m1, mx[3 * i + 1]); m2 = max(m2, mx[3 * i + 2]);
-            }
-            m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2);
-            if ((tid & 63) == 0) { red[3 * (tid >> 6)] = m0; red[3 * (tid >> 6) + 1] = m1; red[3 * (tid >> 6) + 2] = m2; }
+            for (uint32_t i = tid + blockDim.x; i < G; i += blockDim.x) m.take(mx, i);
+            mx3_wave_to_red(m, red, tid);
         }
     }
     lds_barrier();
-    // ---- degree of poly_k (reference degree field; see DevState), uniform ----
-    int deg = -1;
-    bool noncanon = false;                         // layer 0: an input coefficient >= p
-    if (COMMIT) {
-        int m0 = -1, m1 = -1, m2 = -1;
-#pragma unroll
-        for (int i = 0; i < 8; i++) { m0 = max(m0, red[3 * i]); m1 = max(m1, red[3 * i + 1]); m2 = max(m2, red[3 * i + 2]); }
-        deg = (t.k == 0) ? m0 : (m1 < 0 ? m2 : m0);
-        noncanon = t.k == 0 && m1 >= 0;
-    }
-    const bool is_final = COMMIT && deg < 1;
+    // ---- degree of poly_k, uniform ----
+    const Degree dg = COMMIT ? degree_of(t.k, mx3_from_red(red, 8)) : Degree{-1, false};
+    const bool is_final = COMMIT && dg.deg < 1;
     const int job_end = is_final ? CJ_END_FINAL : CJ_END_ROUND;
     uint32_t fv = 0;                               // fri_commit.rs:109-113
-    if (chan_wave && is_final && deg == 0)
+    if (chan_wave && is_final && dg.deg == 0)
         fv = SHARD ? t.shard->recs_in[11] : (t.k == 0 ? t.coef_in : t.coef_out)[0];
-    TOP_STAMP(1);
-    TOP_CLK(17);
+    STAMP(COMMIT && tid == 0, 1);
+    STAMP_CLK(COMMIT && tid == 0, 17);
     // iterations: the levels, then one in which wave 7 runs every channel
     // job still left (no barrier between the post-root jobs)
     const uint32_t nlev = L - l;
     const uint32_t total = nlev + (COMMIT ? 1u : 0u);
-    const uint32_t it_root = COMMIT ? nlev : ~0u;  // the iteration of job 3 (the root's first block)
-    const bool chan_prod = FRI_SCHED_CHANNEL && COMMIT && tid >= 384 && tid < 448;   // wave 6 (SIMD 2)
     const shaq::Role R = shaq::role_of(tid);
     uint32_t cnt = N;
 #pragma unroll 1
@@ -838,115 +857,38 @@ __global__ __launch_bounds__(512) void k_tree_top(LayerTask t, uint32_t l, const
         const bool level = it < nlev;
         if (level) {
             cnt >>= 1;
-            uint32_t* out = tr + 8 * level_offset(L, l + 1 + it);
-            if (cnt <= 128) {                   // waves 0-3, one per SIMD (wave 7: channel)
-#ifdef FRI_STAMPS
-                if (it < 18 && tid == 0) TOP_CLK(24 + 2 * it);
-#endif
-                pair_level_s(A, B, out, tid, cnt, R, &sl, it);
-#ifdef FRI_STAMPS
-                if (it < 18 && tid == 0) TOP_CLK(25 + 2 * it);
-#endif
-            } else {
-#pragma unroll 1
-                for (uint32_t q = tid; q < cnt; q += blockDim.x) {
-                    Dg a, b, o;
-                    dg_lds_load(A + 4 * q, a);
-                    dg_lds_load(A + 4 * q + 2, b);
-#ifdef FRI_STAMPS
-                    if (it < 18 && q == 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TOP_CLK(24 + 2 * it); }
-#endif
-                    cnode(a, b, o);
-#ifdef FRI_STAMPS
-                    if (it < 18 && q == 0) TOP_CLK(25 + 2 * it);
-#endif
-                    dg_lds_store(B + 2 * q, o);
-                    dg_store(out + 8 * q, o);
-                }
-            }
+            level_step(t, COMMIT, it, A, B, tr + 8 * level_offset(L, l + 1 + it), cnt, R, &sl, it);
         }
-        // channel job: during the narrow levels (SIMD 3 idle) only the
-        // pre-root jobs, after the last level anything left
-        if (chan_wave && job < job_end && (level ? (cnt <= 192 && job < CJ_ROOT) : true)) {
-            do {
-#ifdef FRI_STAMPS
-                if (job == CJ_ROOT) TOP_STAMP_T(14, 448);           // job 3 / job 5 start (14, 13)
-                if (job == CJ_ROOT + 2) TOP_STAMP_T(13, 448);
-#endif
-                chan_job(job, cs, X, has, A, fv, R, FRI_SCHED_CHANNEL ? sl.wk : nullptr, &sl.flag, 3u * it_root);
-#ifdef FRI_STAMPS
-                if (job >= CJ_ROOT && job <= CJ_ROOT + 2) TOP_STAMP_T(20 + job - CJ_ROOT, 448);   // done (20..22)
-#endif
-                job++;
-            } while (!level && job < job_end);
-        }
-        if (chan_prod && it == it_root) chan_produce(A, &sl, 3u * it_root, R);
+        if (chan_wave) job = chan_drain(t, job, job_end, level, cnt, cs, X, has, A, fv, R);
         lds_barrier();
         if (level) {
             uint4* tmp = A; A = B; B = tmp;
-            if (it < 11) TOP_STAMP(2 + it);
-            if (it + 1 == nlev) { TOP_CLK(18); TOP_STAMP(19); }
+            STAMP(COMMIT && tid == 0 && it < 11, 2 + it);
+            STAMP_CLK(COMMIT && tid == 0 && it + 1 == nlev, 18);
+            STAMP(COMMIT && tid == 0 && it + 1 == nlev, 19);
         }
     }
     if (SHARD && !COMMIT && tid == 448) {          // this rank's record
         const ShardTop& sh = *t.shard;
-        int m0 = -1, m1 = -1, m2 = -1;
-#pragma unroll
-        for (int i = 0; i < 8; i++) { m0 = max(m0, red[3 * i]); m1 = max(m1, red[3 * i + 1]); m2 = max(m2, red[3 * i + 2]); }
+        const Mx3 m = mx3_from_red(red, 8);
         Dg root;
         dg_lds_load(A, root);
         uint32_t* rec = sh.rec_out;
         dg_store(rec, root);
-        reinterpret_cast<uint4*>(rec)[2] = make_uint4((uint32_t)m0, (uint32_t)m1, (uint32_t)m2, sh.rec_c0[0]);
+        reinterpret_cast<uint4*>(rec)[2] = make_uint4((uint32_t)m.m0, (uint32_t)m.m1, (uint32_t)m.m2, sh.rec_c0[0]);
         reinterpret_cast<uint4*>(rec)[3] = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (!COMMIT || tid != 448) return;
-    // ---- results (wave 7, one lane) ----
-    const int k = t.k;
-    if (noncanon) {                                // FRI_EINVAL: nothing of this commit is served
-        st->active[k] = 0;
-        st->status = 1u;
-        return;
-    }
-    st->deg[k] = deg;
-    Dg root;
-    dg_lds_load(A, root);
-#pragma unroll
-    for (int i = 0; i < 8; i++) st->roots[k][i] = root.w[i];
-    st->n_layers = (uint32_t)k + 1;
-    TOP_STAMP_T(15, 448);
-    if (deg >= 1 && k < MAXR && L >= 1) {
-        uint32_t beta = chan_beta(cs);
-#pragma unroll
-        for (int i = 0; i < 8; i++) st->chan[i] = cs[i];
-        st->chan_has = 1;
-        st->chan_pending = 1;                        // receive's rehash deferred to the next top
-        if (forced) beta = fbeta;
-        st->beta[k] = beta;
-        st->beta_mont[k] = to_mont(beta);
-        st->active[k] = 1;
-        st->n_rounds = (uint32_t)k + 1;
-        TOP_STAMP_T(16, 448);
-    } else {
-        st->active[k] = 0;
-        if (deg >= 1) { st->status = 7u; return; }            // FRI_EDEGREE
-#pragma unroll
-        for (int i = 0; i < 8; i++) st->chan[i] = cs[i];      // after send(final.to_bytes())
-        st->final_value = fv;
-        st->final_degree = deg;
-        st->chan_has = 1;
-        st->chan_pending = 0;
-    }
+    if (COMMIT && tid == 448) layer_results(t, dg, cs, fv, fbeta1, A);
 }
 
 // ------------------------------------------------------------- tail ----
 // The last layers of a commit (2^L <= 2^TAIL_LOG elements each) in ONE
-// workgroup and ONE launch: per layer the body of k_tree_top<true, *, true>
-// (fold, leaves, coefficient fold, degree, tree levels, channel step), with
-// the layer values, the coefficients, beta, the degree and the gate handed to
-// the next layer through LDS.  Saves per layer a kernel boundary, the HBM
-// round trip of the folded values and coefficients, and the cold first level
-// of a fresh workgroup.  The channel state stays in wave 7's registers.
+// workgroup and ONE launch: per layer the fold, the leaves, the coefficient
+// fold, the degree, the tree levels and the channel step (the helpers above),
+// with the layer values, the coefficients, beta, the degree and the gate
+// handed to the next layer through LDS.  Saves per layer a kernel boundary,
+// the HBM round trip of the folded values and coefficients, and the cold first
+// level of a fresh workgroup.  The channel state stays in wave 7's registers.
 struct TailTask {
     LayerTask t[TAIL_LOG + 1];  // consecutive layers k0 .. k0 + n - 1 (commit mode)
     uint32_t n;
@@ -964,11 +906,11 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
     __shared__ int32_t red[24];
     __shared__ uint32_t s_beta_m, s_active;
     __shared__ int32_t s_deg;
-    __shared__ uint32_t s_fbeta[TAIL_LOG + 2];   // the test hook's betas of these layers (0: not forced)
+    __shared__ uint32_t s_fbeta[TAIL_LOG + 2];   // the test hook's betas of these layers (layer_results' fbeta1)
     __shared__ uint32_t xv[2 * NMAX];            // every layer's x^-1 table (prefetched)
     __shared__ SchedLds sl;
     sched_init(&sl);
-    uint32_t ord = 0;                            // narrow levels so far (schedule producer flag)
+    uint32_t ord = 0;                            // levels so far (schedule producer flag)
     const uint32_t tid = threadIdx.x;
     const bool chan_wave = tid >= 448;
     DevState* st = t0.st;
@@ -1016,27 +958,20 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
         uint4* A = lds;
         uint4* B = lds + 2 * NMAX;
         uint32_t* tr = t.tree;
-        TAIL_STAMP(0);
-        // ---- fold + leaves (spare lanes of wave 0 recompute leaf i mod N) ----
-        for (uint32_t i = tid; i < max(N, 64u); i += blockDim.x) {
-            const uint32_t j = i & (N - 1);
-            const bool real = i < N;
+        STAMP(tid == 0, 0);
+        // ---- fold + leaves: layer li >= 1 folds the values kept in LDS ----
+        leaf_loop(N, tr, A, [&](uint32_t j, bool real) {
             uint32_t v;
             if (fold) {
                 const uint32_t a = li ? prev_v[j] : t.prev[j], b = li ? prev_v[j + N] : t.prev[j + N];
-                v = fold1(a, b, xl[j], beta_m);
+                v = fold_one(a, b, xl[j], beta_m);
                 if (real) t.values[j] = v;
             } else {
                 v = t.values[j];
             }
             if (real) cur_v[j] = v;
-            Dg d;
-            cleaf(v, d);
-            if (real) {
-                dg_store(tr + 8 * j, d);
-                dg_lds_store(A + 2 * j, d);
-            }
-        }
+            return v;
+        });
         // ---- coefficient fold of round k-1 (or the input scan at k == 0) ----
         // Needed only for the degree, i.e. from the root on: it runs on waves
         // 4-5 (threads [256, 384)) during the first level iteration that
@@ -1045,13 +980,13 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
         const uint32_t coef_it = N > 256 ? 1u : 0u;   // iteration 0 of a 512-leaf layer uses all waves
         const bool coef_late = nlev > coef_it;
         auto coef_fold = [&](uint32_t t0c, uint32_t nthr) {
-            int m0 = -1, m1 = -1, m2 = -1;
+            Mx3 m;
             const uint32_t tx = tid - t0c;
             if (k == 0) {
                 for (size_t j = tx; j < t.d0; j += nthr) {
                     const uint32_t c = t.coef_in[j];
-                    if (c) m0 = max(m0, (int)j);
-                    if (c >= P) m1 = 0;                    // not canonical (see coef_task)
+                    if (c) m.m0 = max(m.m0, (int)j);
+                    if (c >= P) m.m1 = 0;                  // not canonical (see Mx3)
                 }
             } else {
                 const uint32_t len = (uint32_t)(prev_deg + 1), nlen = (len + 1) / 2;
@@ -1061,129 +996,60 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
                     const uint32_t o = (2 * j + 1 < len) ? (in_lds ? prev_c[2 * j + 1] : t.coef_in[2 * j + 1]) : 0u;
                     const uint32_t v = add(e, mmul(o, beta_m));
                     cur_c[j] = v;
-                    if (v) m0 = (int)j;
-                    if (e) m1 = (int)j;
-                    if (o) m2 = (int)j;
+                    if (v) m.m0 = (int)j;
+                    if (e) m.m1 = (int)j;
+                    if (o) m.m2 = (int)j;
                 }
             }
-            m0 = wave_max_i(m0); m1 = wave_max_i(m1); m2 = wave_max_i(m2);
-            const uint32_t w = tx >> 6;
-            if ((tx & 63) == 0) { red[3 * w] = m0; red[3 * w + 1] = m1; red[3 * w + 2] = m2; }
+            mx3_wave_to_red(m, red, tx);
         };
         if (!coef_late) coef_fold(0, blockDim.x);
         if (li == 0 && !coef_late) prefetch_x(0, blockDim.x);
         lds_barrier();
-        TAIL_STAMP(1);
-        TAIL_CLK(17);
-        int deg = 1;
-        bool noncanon = false;
+        STAMP(tid == 0, 1);
+        STAMP_CLK(tid == 0, 17);
+        Degree dg{1, false};
         int job_end = CJ_END_ROUND;                    // provisional while the degree is pending
         uint32_t fv = 0;                               // fri_commit.rs:109-113
         // red[] (after a barrier) -> degree of poly_k; is it the last layer?
         auto settle = [&](uint32_t nw) {
-            int a = -1, b = -1, c = -1;
-            for (uint32_t i = 0; i < nw; i++) { a = max(a, red[3 * i]); b = max(b, red[3 * i + 1]); c = max(c, red[3 * i + 2]); }
-            deg = (k == 0) ? a : (b < 0 ? c : a);
-            noncanon = k == 0 && b >= 0;
-            job_end = deg < 1 ? CJ_END_FINAL : CJ_END_ROUND;
-            if (chan_wave && deg == 0) fv = (k == 0) ? t.coef_in[0] : cur_c[0];
+            dg = degree_of(k, mx3_from_red(red, nw));
+            job_end = dg.deg < 1 ? CJ_END_FINAL : CJ_END_ROUND;
+            if (chan_wave && dg.deg == 0) fv = (k == 0) ? t.coef_in[0] : cur_c[0];
         };
         if (!coef_late) settle(8);
-        // ---- levels + channel jobs (k_tree_top) ----
+        // ---- levels + channel jobs ----
         int job = CJ_END_FINAL;
         if (chan_wave) job = !has ? CJ_ROOT : (pending ? CJ_REHASH : CJ_MID);
         // the levels, then one iteration in which wave 7 runs every channel
         // job still left (their number follows the degree, settled by then)
         const uint32_t total = nlev + 1;
-        const uint32_t it_root = nlev;                                // iteration of job 3
-        uint32_t ch_base = 0;                                         // flag base of this layer's root blocks
         uint32_t cnt = N;
 #pragma unroll 1
         for (uint32_t it = 0; it < total; it++) {
             const bool level = it < nlev;
             if (level) {
                 cnt >>= 1;
-                uint32_t* out = tr + 8 * level_offset(L, 1 + it);
-                if (cnt <= 128) {
-                    if (it < 18) TAIL_CLK(24 + 2 * it);
-                    pair_level_s(A, B, out, tid, cnt, R, &sl, ord++);
-                    if (it < 18) TAIL_CLK(25 + 2 * it);
-                } else {
-#pragma unroll 1
-                    for (uint32_t q = tid; q < cnt; q += blockDim.x) {
-                        Dg a, b, o;
-                        dg_lds_load(A + 4 * q, a);
-                        dg_lds_load(A + 4 * q + 2, b);
-                        cnode(a, b, o);
-                        dg_lds_store(B + 2 * q, o);
-                        dg_store(out + 8 * q, o);
-                    }
-                }
+                level_step(t, true, it, A, B, tr + 8 * level_offset(L, 1 + it), cnt, R, &sl, ord++);
             }
-            if (!level && it == it_root) ch_base = 3u * (ord++), ord++;   // two ordinals (uniform)
-            if (chan_wave && job < job_end && (level ? (cnt <= 192 && job < CJ_ROOT) : true)) {
-                do {
-                    chan_job(job, cs, X, has, A, fv, R, FRI_SCHED_CHANNEL ? sl.wk : nullptr, &sl.flag, ch_base);
-#ifdef FRI_STAMPS
-                    if (job >= CJ_ROOT && job <= CJ_ROOT + 2) TAIL_STAMP_T(20 + job - CJ_ROOT, 448, __builtin_amdgcn_s_memrealtime);
-#endif
-                    job++;
-                } while (!level && job < job_end);
-            }
-            if (FRI_SCHED_CHANNEL && tid >= 384 && tid < 448 && !level && it == it_root) chan_produce(A, &sl, ch_base, R);
+            if (chan_wave) job = chan_drain(t, job, job_end, level, cnt, cs, X, has, A, fv, R);
             if (coef_late && it == coef_it && tid >= 256 && tid < 384) coef_fold(256, 128);
             if (li == 0 && coef_late && it == coef_it && tid >= 384 && tid < 448) prefetch_x(384, 64);
             lds_barrier();
             if (coef_late && it == coef_it) settle(2);
             if (level) {
                 uint4* tmp = A; A = B; B = tmp;
-                if (it < 11) TAIL_STAMP(2 + it);
-                if (it + 1 == nlev) { TAIL_CLK(18); TAIL_STAMP(19); }
+                STAMP(tid == 0 && it < 11, 2 + it);
+                STAMP_CLK(tid == 0 && it + 1 == nlev, 18);
+                STAMP(tid == 0 && it + 1 == nlev, 19);
             }
         }
         // ---- results (one lane of wave 7), hand-off to the next layer ----
-        if (tid == 448 && noncanon) {                   // FRI_EINVAL (uniform: the loop ends below)
-            st->active[k] = 0;
-            st->status = 1u;
-            s_active = 0;
-        } else if (tid == 448) {
-            st->deg[k] = deg;
-            Dg root;
-            dg_lds_load(A, root);
-#pragma unroll
-            for (int i = 0; i < 8; i++) st->roots[k][i] = root.w[i];
-            st->n_layers = (uint32_t)k + 1;
-            uint32_t active = 0, bm = 0;
-            if (deg >= 1 && k < MAXR && L >= 1) {
-                uint32_t beta = chan_beta(cs);
-#pragma unroll
-                for (int i = 0; i < 8; i++) st->chan[i] = cs[i];
-                st->chan_has = 1;
-                st->chan_pending = 1;                    // receive's rehash deferred to the next layer
-                if (s_fbeta[li]) beta = s_fbeta[li] - 1u;
-                st->beta[k] = beta;
-                bm = to_mont(beta);
-                st->beta_mont[k] = bm;
-                st->active[k] = 1;
-                st->n_rounds = (uint32_t)k + 1;
-                active = 1;
-            } else {
-                st->active[k] = 0;
-                if (deg >= 1) {
-                    st->status = 7u;                     // FRI_EDEGREE
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; i++) st->chan[i] = cs[i];   // after send(final.to_bytes())
-                    st->final_value = fv;
-                    st->final_degree = deg;
-                    st->chan_has = 1;
-                    st->chan_pending = 0;
-                }
-            }
-            s_beta_m = bm;
-            s_active = active;
-            s_deg = deg;
-            TAIL_STAMP_T(15, 448, __builtin_amdgcn_s_memrealtime);
+        if (tid == 448) {
+            const RoundOut r = layer_results(t, dg, cs, fv, s_fbeta[li], A);
+            s_beta_m = r.beta_m;
+            s_active = r.active;
+            s_deg = dg.deg;
         }
         if (chan_wave) { has = 1; pending = 1; }
         lds_barrier();
@@ -1194,20 +1060,33 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
 }
 
 // ------------------------------------------------------------ launcher ----
-// Layer schedule (levels are consumed 4 at a time):
-//   L <= 9 : one k_tree_top from the leaves.
-//   L >= 19: k_layer_leaf (2048 leaves/WG -> 128);  11..18: k_layer_leaf_wide (256 -> 16)
-//   then k_tree_mid<1024> while the level has >= 2^18 nodes, k_tree_mid<256>
-//   while it has > 512, and k_tree_top on the last <= 512 nodes.
+// Layer schedule of launch_layer (D = L - l: log2 of the nodes still to climb):
+//   L <= 9 : one k_tree_top from the leaves (standalone trees only; a commit
+//            sends these layers to launch_tail).
+//   L >= 19: k_layer_leaf (2048 leaves/WG, levels 1..4);  10..18:
+//            k_layer_leaf_wide (256 leaves/WG, levels 1..8, or 1..4 at L == 18)
+//   then k_tree_mid (4 levels) while D >= 18, one k_tree_mid8 (8 levels) if
+//   D > 9 is left, and k_tree_top on the last <= 512 nodes.
+// After the leaf kernel D is <= 9 (L <= 17), 14 (L == 18) or L - 4 >= 15, and
+// k_tree_mid takes D from >= 18 to >= 14: the loop never sees 10 <= D <= 13,
+// so one k_tree_mid8 always leaves 6 <= D <= 9 for the top.
+//
+// k_tree_top instantiations <FROM_LEAVES, COMMIT, SHARD> and who reaches them:
+//   <true,  false>        fri_merkle_root, fri_trace_commit with L <= 9 (no prev, no st)
+//   <false, false>        the same two callers with L >= 10
+//   <false, false, true>  run_commit_sharded's block trees (st null, shard set): L = log2 block >= 10
+//   <false, true>         enqueue_commit and the sharded local tail, layers of L >= 10
+//   <false, true,  true>  launch_top: the replicated top of a sharded layer
+// Not built: from the leaves in commit mode (both commit drivers send every
+// layer of L <= TAIL_LOG == TOP_LOG to launch_tail) and from the leaves with
+// a fold outside a commit (only the sharded block trees fold without st, and
+// next_layer_sharded keeps their blocks at >= 2^10 elements).
 static LayerTask with_gate(const LayerTask& in) {
     LayerTask t = in;
     if (t.st) { t.gst = t.st; t.gidx = t.k > 0 ? t.k - 1 : -1; }
     return t;
 }
 
-#ifndef MID8
-#define MID8 1               // k_tree_mid8 for the narrow levels of large layers
-#endif
 #ifndef QUAD_TPB
 #define QUAD_TPB 512         // quad leaf kernel: threads per WG (2048 leaves per WG; A/B: 512 beats 256 by ~0.5-1%, 128 and 1024 slower)
 #endif
@@ -1243,14 +1122,10 @@ void launch_layer(const LayerTask& tin, hipStream_t s, hipEvent_t ev_leaf_end, c
     const bool commit = t.st != nullptr;
     const bool pair = t.prev2 != nullptr;          // sharded block tree, pair fold fused (never commit mode)
     const int32_t* nomx = nullptr;
+    static_assert(TAIL_LOG == TOP_LOG, "every commit layer the top could take from its leaves goes to launch_tail");
     if (L <= TOP_LOG) {
-        if (fold) {
-            if (commit) hipLaunchKernelGGL((k_tree_top<true, true, true>), dim3(1), dim3(512), 0, s, t, 0u, nomx, 1u);
-            else hipLaunchKernelGGL((k_tree_top<true, true, false>), dim3(1), dim3(512), 0, s, t, 0u, nomx, 1u);
-        } else {
-            if (commit) hipLaunchKernelGGL((k_tree_top<true, false, true>), dim3(1), dim3(512), 0, s, t, 0u, nomx, 1u);
-            else hipLaunchKernelGGL((k_tree_top<true, false, false>), dim3(1), dim3(512), 0, s, t, 0u, nomx, 1u);
-        }
+        assert(!fold && !commit);                  // see the reachability table above
+        hipLaunchKernelGGL((k_tree_top<true, false>), dim3(1), dim3(512), 0, s, t, 0u, nomx, 1u);
         if (ev_leaf_end) hipEventRecord(ev_leaf_end, s);
         return;
     }
@@ -1294,28 +1169,26 @@ void launch_layer(const LayerTask& tin, hipStream_t s, hipEvent_t ev_leaf_end, c
     uint32_t l = L >= QUAD_MIN_LOG ? 4u : wide_levels(L);
     while (L - l > TOP_LOG) {
         const size_t nodes = (size_t)1 << (L - l);
-        const uint32_t nin = nodes >= ((size_t)1 << 18) ? 1024u : 256u;
+        // eight narrow levels in one launch once the level has < 2^18 nodes
+        const bool eight = nodes < ((size_t)1 << 18);
+        assert(!eight || L - l >= 8 + 6);          // see the schedule above
+        const uint32_t nin = eight ? 256u : 1024u;
         const uint32_t grid = (uint32_t)(nodes / nin);
         const uint32_t R = nin / out_per_wg;
         int32_t* mx_out = commit ? t.wgmax + mx_off : nullptr;
-        // eight narrow levels in one launch when four would leave more than
-        // the top takes (L - l >= 14: two k_tree_mid<256> otherwise)
-        const bool eight = nin == 256 && L - l >= 8 + 6 && MID8;
-        if (nin == 1024)
-            hipLaunchKernelGGL((k_tree_mid<1024>), dim3(grid), dim3(512), 0, s, t.tree, L, l, t.gst, gate, mx, mx_out, R);
-        else if (eight)
+        if (eight)
             hipLaunchKernelGGL(k_tree_mid8, dim3(grid), dim3(256), 0, s, t.tree, L, l, t.gst, gate, mx, mx_out, R);
         else
-            hipLaunchKernelGGL((k_tree_mid<256>), dim3(grid), dim3(128), 0, s, t.tree, L, l, t.gst, gate, mx, mx_out, R);
+            hipLaunchKernelGGL(k_tree_mid, dim3(grid), dim3(512), 0, s, t.tree, L, l, t.gst, gate, mx, mx_out, R);
         if (commit) { mx = mx_out; mx_off += 3 * (size_t)grid; }
         G = grid;
         out_per_wg = eight ? 1u : nin / 16;
         l += eight ? 8u : 4u;
     }
     if (ev_before_top) hipStreamWaitEvent(s, ev_before_top, 0);
-    if (commit) hipLaunchKernelGGL((k_tree_top<false, false, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
-    else if (t.shard) hipLaunchKernelGGL((k_tree_top<false, false, false, true>), dim3(1), dim3(512), 0, s, t, l, nomx, G);
-    else hipLaunchKernelGGL((k_tree_top<false, false, false>), dim3(1), dim3(512), 0, s, t, l, nomx, G);
+    if (commit) hipLaunchKernelGGL((k_tree_top<false, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
+    else if (t.shard) hipLaunchKernelGGL((k_tree_top<false, false, true>), dim3(1), dim3(512), 0, s, t, l, nomx, G);
+    else hipLaunchKernelGGL((k_tree_top<false, false>), dim3(1), dim3(512), 0, s, t, l, nomx, G);
 }
 
 void launch_tail(const LayerTask* ts, uint32_t n, hipStream_t s) {
@@ -1340,8 +1213,8 @@ void launch_coef(const LayerTask& tin, uint32_t G, hipStream_t s) {
 
 void launch_top(const LayerTask& tin, uint32_t l, const int32_t* mx, uint32_t G, hipStream_t s) {
     const LayerTask t = with_gate(tin);
-    if (t.shard) hipLaunchKernelGGL((k_tree_top<false, false, true, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
-    else hipLaunchKernelGGL((k_tree_top<false, false, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
+    if (t.shard) hipLaunchKernelGGL((k_tree_top<false, true, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
+    else hipLaunchKernelGGL((k_tree_top<false, true>), dim3(1), dim3(512), 0, s, t, l, mx, G);
 }
 
 }  // namespace fri

@@ -38,7 +38,6 @@ extern "C" int fri_lde(fri_ctx* ctx, const uint32_t* coeffs, size_t d, uint32_t 
     launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_n, offset, 1u, ctx->stream);
     p.pre_lo = ctx->pow_lo;
     p.pre_hi = ctx->pow_hi;
-    p.scratch = ctx->scratch_c;
     launch_ntt(p, ctx->scratch_a, d, ctx->scratch_b, ctx->stream);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(evals_out, ctx->scratch_b, n * 4, hipMemcpyDeviceToHost, ctx->stream));

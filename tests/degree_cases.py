@@ -314,7 +314,7 @@ def _gpu_specs():
         assert name not in s
         s[name] = (fn, a, dict(kw, name=name))
 
-    # 2^23, d = 2^20: layer 1 has L = 22 (quad leaf, k_tree_mid<1024> with R = 8,
+    # 2^23, d = 2^20: layer 1 has L = 22 (quad leaf, k_tree_mid with R = 8,
     # k_tree_mid8 with R = 4, top over 64).  nlen = 2^19 over 2048 workgroups.
     add("23_cancel_first_quarter", cancel, 23, 1 << 20, 0, 70001, 2301)
     add("23_beta_zero_two_mid_groups", beta_zero, 23, 1 << 20, 0, 300007, 131101, 2302)

@@ -4,7 +4,7 @@ fri_commit ends when the folded polynomial's degree falls below 1.  On the
 device that degree is a max-reduction of three values per fold (m0, m1, m2:
 the last non-zero index of the folded coefficients, of the even and of the odd
 part) through coef_slice / coef_combine in the leaf-kernel workgroups, the
-mx -> mx_out pass of every k_tree_mid<1024> / k_tree_mid8 launch, the per-wave
+mx -> mx_out pass of every k_tree_mid / k_tree_mid8 launch, the per-wave
 triples of k_tree_top, the LDS copy inside k_tree_tail and, sharded, the rank
 records.  A dense polynomial under a channel-drawn beta keeps m0 = m1 = m2 =
 nlen - 1 in the last workgroup with work, whatever those stages do with the

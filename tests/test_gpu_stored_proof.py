@@ -1,7 +1,7 @@
 """GPU: what a commit leaves in HBM, node for node against the C oracle.
 
 A right root does not imply right stored levels: the leaf, mid and top
-kernels (k_layer_leaf, k_layer_leaf_wide, k_tree_mid<1024>, k_tree_mid8,
+kernels (k_layer_leaf, k_layer_leaf_wide, k_tree_mid, k_tree_mid8,
 k_tree_top, k_tree_tail; csrc/fri_layer.hip) keep a subtree in registers, DPP
 lanes or LDS, and only the last level a kernel writes is read back by the
 next one.  Every other level, and every layer's values past the next fold, is
@@ -22,19 +22,12 @@ fold on the layers below it:
   2^10..2^17  k_layer_leaf_wide with 8 levels, then a top over 4, 32, 512 nodes
   2^18        wide leaf with 4 levels, k_tree_mid8, top
   2^19, 2^21  quad k_layer_leaf, k_tree_mid8, a top over 128 and 512 nodes
-  2^22        quad leaf, k_tree_mid<1024>, k_tree_mid8, top: the smallest size
+  2^22        quad leaf, k_tree_mid, k_tree_mid8, top: the smallest size
               that reaches every kernel (larger ones add grid size and a
-              second k_tree_mid<1024>, no new store path).
+              second k_tree_mid, no new store path).
 
-k_tree_mid<256> is unreachable: launch_layer is the only launcher of the mid
-kernels (commit, sharded block trees, fri_merkle_root and fri_trace_commit all
-go through it), and with MID8 = 1 its loop launches k_tree_mid<256> only for
-10 <= L - l <= 13 on a level of fewer than 2^18 nodes.  The loop is entered
-with L - l = 14 (L = 18, wide leaf, 4 levels) or L - 4 >= 15 (quad leaf);
-k_tree_mid<1024> runs while L - l >= 18 and leaves L - l in 14..17; every
-value in 14..17 takes k_tree_mid8, which leaves L - l in 6..9, the top's.
-L <= 17 never enters the loop (wide leaf, 8 levels, L - 8 <= 9).  So no size
-exercises it, and no test here can."""
+The mid kernels have no other size class: launch_layer's loop takes k_tree_mid
+while L - l >= 18 and then k_tree_mid8 once (the argument is in its comment)."""
 import ctypes
 
 import numpy as np
@@ -88,7 +81,7 @@ def _big_resident(ctx, big):
 
 
 def test_stored_proof_matches_oracle_2p22(ctx, big):
-    """Quad leaf, k_tree_mid<1024>, k_tree_mid8 and top on layer 0, and every
+    """Quad leaf, k_tree_mid, k_tree_mid8 and top on layer 0, and every
     smaller schedule behind a fused fold below it: 2^23 values and 2^23 nodes."""
     full = _big_resident(ctx, big)
     assert full.n_layers == BIG - 2
