@@ -123,18 +123,68 @@ int fri_interpolate(fri_ctx* ctx, const uint32_t* ys, uint32_t log_n, uint32_t o
  * (src/polynomial/ops.rs:239-241 -> interpolate_lagrange_polynomials,
  * interpolation.rs:121-152) for point sets that are not a coset.  Same
  * result as the reference's Lagrange sum, duplicates included (their basis
- * polynomials vanish through inverse(0) = 0, element.rs:54-57).  O(n^2) on
- * the device: weights w_j = 1/prod_{i!=j}(x_j - x_i), then f at the 2^k-th
- * roots of unity (2^k >= n) as the polynomial sum_j y_j w_j prod_{i!=j}(x - x_i)
- * without any division, then an iNTT.  n <= 2^17 and n <= 2^log_n_max.
- * coeffs_out holds n entries; *len_out = trimmed length. */
+ * polynomials vanish through inverse(0) = 0, element.rs:54-57).  Two paths,
+ * the same coefficients (field arithmetic is exact):
+ *   direct  O(n^2): weights w_j = 1/prod_{i!=j}(x_j - x_i), then f at the
+ *           2^k-th roots of unity (2^k >= n) as sum_j y_j w_j prod_{i!=j}(x - x_i)
+ *           without any division, then an iNTT.  n <= 2^17, n <= 2^log_n_max.
+ *   tree    O(n log^2 n), from n >= FRI_MP_INTERP_MIN: the product tree of
+ *           fri_poly_from_roots with every level retained, the weights as
+ *           1/Z'(x_i) by the tree evaluation below, then sum_i y_i w_i Z/(x - x_i)
+ *           combined up the tree.  Accepted sizes are exactly
+ *             next_pow2(n) <= 2^(log_n_max - 1)
+ *           (Z' has n coefficients and is evaluated at next_pow2(n) points).
+ * fri_interpolate_points is fri_interpolate_points_ex with flags 0: the tree
+ * from FRI_MP_INTERP_MIN points where the sizes fit, else the direct kernels with the
+ * launches they always had.  coeffs_out holds n entries; *len_out = trimmed
+ * length; n = 0 gives length 0. */
 int fri_interpolate_points(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys, size_t n,
                            uint32_t* coeffs_out, size_t* len_out);
 
 /* Evaluation of P (d coefficients) at `count` arbitrary points
- * (src/polynomial/ops.rs:76-83, Horner semantics). */
+ * (src/polynomial/ops.rs:76-83, Horner semantics): fri_evaluate_ex with
+ * flags 0.  d = 0 gives zeros, count = 0 writes nothing. */
 int fri_evaluate(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs,
                  size_t count, uint32_t* out);
+
+/* The two calls above with a choice of path.  The tree path pads the point
+ * list with zero roots to N = next_pow2(count), builds the product tree with
+ * every level from the leaf subtrees up retained in the context's grown
+ * scratch, inverts rev(Z_pad) as a power series to d terms (Newton, as
+ * fri_poly_div_rem), takes the vector of f / Z_pad from one product of cyclic
+ * size next_pow2(d + N - 1) and goes down the tree with one batched set of
+ * cyclic middle products per level (a fixed number of launches whatever the
+ * node count); in a leaf subtree one lane per point finishes with a synthetic
+ * division chain.  Values equal Horner's bit for bit.  Accepted sizes of the
+ * tree path are exactly
+ *   d + next_pow2(count) - 1 <= 2^log_n_max  and  next_pow2(d) <= 2^(log_n_max - 1)
+ * (the root product and the last Newton step).  FRI_MP_FORCE_TREE outside
+ * them gives FRI_EINVAL; flags 0 then runs the direct kernels where they
+ * accept the call.  Both FORCE flags together, or an unknown flag, give
+ * FRI_EINVAL.  The leaf subtrees hold FRI_ROOTS_LEAF points
+ * (fri_debug_set_roots_leaf applies).  Memory: the retained levels are
+ * (log2 N - log2 leaf + 1) * N words, 48 MiB at N = 2^20 and 1 GiB at 2^24
+ * with leaves of 512, next to about 8 N words of vectors and operands (13 N
+ * for interpolation); a failed allocation gives FRI_ENOMEM and leaves the
+ * context usable.  On a multi-GPU context the calls run on rank 0. */
+#define FRI_MP_FORCE_TREE   1u   /* test/measurement hook: never the direct kernels */
+#define FRI_MP_FORCE_DIRECT 2u   /* test/measurement hook: always them (FRI_EINVAL past their limits) */
+#define FRI_MP_SMALL_LEAF   4u   /* test hook: leaf subtrees of 64 points */
+/* Evaluation takes the tree when min(d, count) >= FRI_MP_EVAL_MIN,
+ * interpolation when n >= FRI_MP_INTERP_MIN (and the sizes fit): the measured
+ * crossovers (profiles/poly_multipoint.txt, from tools/poly_arith_probe.py
+ * --multipoint) — the smallest power of two from which the tree is not slower
+ * than the direct kernels, whole call, the same in both runs of the table.
+ * Evaluation, d = count: 0.601 ms direct against 1.535 tree at 2^15, 5.002
+ * against 1.731 at 2^16, 21.8 against 2.30 at 2^18.  Interpolation: 1.251
+ * against 2.057 at 2^15, 4.438 against 2.314 at 2^16, 16.1 against 2.63 at
+ * 2^17.  The tree's cost below 2^15 is its launches (0.5 ms at 2^10). */
+#define FRI_MP_EVAL_MIN     65536
+#define FRI_MP_INTERP_MIN   65536
+int fri_evaluate_ex(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count,
+                    uint32_t flags, uint32_t* out);
+int fri_interpolate_points_ex(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys, size_t n,
+                              uint32_t flags, uint32_t* coeffs_out, size_t* len_out);
 
 /* ------------------------------------------------- polynomial arithmetic */
 /* Polynomial<M>::mul_assign, div_rem and compose (src/polynomial/ops.rs) on

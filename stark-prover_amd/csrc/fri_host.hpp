@@ -2,9 +2,11 @@
 // units of the C ABI (include/fri_amd.h).  One file per concern:
 //   fri_ctx.hip        context lifetime, profiling spans, diagnostics
 //   fri_ops.hip        kernel-level entry points: batch inverse, LDE,
-//                      interpolation, evaluation, fold, Merkle root
+//                      interpolation, fold, Merkle root; the direct kernels of
+//                      arbitrary-point interpolation and evaluation
 //   fri_poly.hip       polynomial arithmetic: mul, div_rem, compose
 //   fri_roots.hip      polynomial from roots (product tree), Lagrange basis
+//   fri_multipoint.hip evaluation and interpolation at arbitrary points, on the tree
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
@@ -414,6 +416,44 @@ inline void tmp_trim(fri_ctx* ctx) {
     ctx->interp_cap = 0;
 }
 
+// ---- polynomial layer helpers (fri_poly.hip, fri_roots.hip, fri_multipoint.hip)
+inline size_t trimmed(const uint32_t* v, size_t n) {              // Polynomial::new (ops.rs:19-37)
+    while (n > 0 && v[n - 1] == 0) n--;
+    return n;
+}
+inline uint32_t ceil_log2(size_t n) {
+    uint32_t l = 0;
+    while (((size_t)1 << l) < n) l++;
+    return l;
+}
+inline size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
+// dst = NTT_{2^log_N}(src[0..len)), natural order, canonical.
+inline void forward(fri_ctx* ctx, const uint32_t* src, size_t len, uint32_t log_N, uint32_t* dst) {
+    NttPlan p = lde_plan(ctx, log_N);
+    launch_ntt(p, src, len, dst, ctx->stream);
+}
+// The inverse transform's post-scale N^-1 * R^r_pow: undoes the r_pow factors
+// of R^-1 a pointwise kernel left (fri_kernels.hip "polynomial arithmetic").
+inline uint32_t post_scale(uint32_t log_N, uint32_t r_pow) {
+    uint32_t scale = inv_std((uint32_t)(((size_t)1 << log_N) % P));
+    for (uint32_t i = 0; i < r_pow; i++) scale = mul_std(scale, R_MOD_P);
+    return scale;
+}
+inline void inverse_with(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, const uint32_t* post_lo,
+                         const uint32_t* post_hi, uint32_t* dst) {
+    NttPlan p{};
+    p.log_n = log_N;
+    p.tw = ctx->tw_inv;
+    p.post_lo = post_lo;
+    p.post_hi = post_hi;
+    launch_ntt(p, src, (size_t)1 << log_N, dst, ctx->stream);
+}
+// dst = N^-1 * R^r_pow * iNTT(src)
+inline void inverse(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, uint32_t r_pow, uint32_t* dst) {
+    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, 1u, post_scale(log_N, r_pow), ctx->stream);
+    inverse_with(ctx, src, log_N, ctx->pow_lo, ctx->pow_hi, dst);
+}
+
 inline void digest_to_bytes(const uint32_t* w, uint8_t* out) {
     for (int i = 0; i < 8; i++) {
         out[4 * i] = (uint8_t)(w[i] >> 24); out[4 * i + 1] = (uint8_t)(w[i] >> 16);
@@ -449,6 +489,17 @@ int commit_finish(fri_ctx* ctx, DevState* h, uint32_t log_n, fri_commit_result* 
 int run_commit(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* dev_coeffs, size_t d, uint32_t log_n,
                uint32_t offset, const fri_channel_state* chan_in, uint32_t flags, const uint32_t* forced_betas,
                fri_commit_result* out);
+
+// ---- fri_roots.hip: the product tree (also under fri_multipoint.hip)
+uint32_t roots_leaf_log(const fri_ctx* ctx, bool small_leaf);   // log2 of the roots per leaf subtree
+const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, uint32_t lf_log,
+                             uint32_t* keep = nullptr);
+
+// ---- fri_ops.hip: the direct kernels behind fri_evaluate_ex / fri_interpolate_points_ex
+// (arguments validated by the caller)
+int evaluate_direct(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count, uint32_t* out);
+int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys, size_t n, uint32_t log_N,
+                              uint32_t* coeffs_out, size_t* len_out);
 
 // ---- fri_readback.hip
 int dq_alloc(fri_ctx* ctx);                   // pinned host buffer the gather kernels write

@@ -125,6 +125,31 @@ void launch_roots_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* out,
 size_t lagrange_tmp_words(size_t n);
 void launch_lagrange_rows(const uint32_t* xs, const uint32_t* z, const uint32_t* w, size_t n, uint32_t* out,
                           uint32_t* tmp, hipStream_t s);
+// Multipoint evaluation and interpolation on the retained tree
+// (fri_multipoint.hip).  a and F levels are canonical, 2^log_np words laid out
+// like the tree's levels; `nodes` is the tree's level below the products.
+// g = F^-1 mod x^cnt (cnt <= 64) for a series of lf words with F[0] = 1
+void launch_mp_series_seed(const uint32_t* F, size_t lf, uint32_t cnt, uint32_t* g, hipStream_t s);
+// out[j] = (j + 1) z[j + 1], j < n (z[n] = 1 implied)
+void launch_mp_derivative(const uint32_t* z, size_t n, uint32_t* out, hipStream_t s);
+// out[i] = f(xs[i]), i < count, from the leaf level's nodes (canonical if canon) and vectors a
+void launch_mp_leaf_eval(const uint32_t* xs, size_t count, const uint32_t* node, bool canon, const uint32_t* a,
+                         uint32_t log_np, uint32_t log_leaf, uint32_t* out, hipStream_t s);
+// out = the F level of the leaf subtrees over xs[0..n), c[0..n) (zero roots and c = 0 beyond n)
+void launch_mp_leaf_up(const uint32_t* xs, const uint32_t* c, size_t n, uint32_t log_np, uint32_t log_leaf,
+                       uint32_t* out, hipStream_t s);
+// one level, products of 2^lg <= 2^ROOTS_LDS_LOG_MAX words: parents' a -> children's a; children's F -> parents' F
+void launch_mp_down_level_lds(const uint32_t* a_in, const uint32_t* nodes, uint32_t* a_out, uint32_t log_np,
+                              uint32_t lg, const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s);
+void launch_mp_up_level_lds(const uint32_t* f_in, const uint32_t* nodes, uint32_t* f_out, uint32_t log_np, uint32_t lg,
+                            const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s);
+// larger levels, on transforms of `words` values: tr = ta (tr + s) / 2^lg, tl = ta (tl + s) / 2^lg;
+// dst's low half of every 2^lg words = src's high half; out = (fl (br + s) + fr (bl + s)) / 2^lg
+void launch_mp_down_pointwise(const uint32_t* ta, uint32_t* tl, uint32_t* tr, size_t words, uint32_t lg,
+                              hipStream_t s);
+void launch_mp_take_high(const uint32_t* src, uint32_t* dst, size_t words, uint32_t lg, hipStream_t s);
+void launch_mp_up_pointwise(const uint32_t* fl, const uint32_t* fr, const uint32_t* bl, const uint32_t* br,
+                            uint32_t* out, size_t words, uint32_t lg, hipStream_t s);
 struct DecommitPlan {
     uint64_t index;
     uint32_t log_n, n_layers;

@@ -1251,4 +1251,352 @@ void launch_lagrange_rows(const uint32_t* xs, const uint32_t* z, const uint32_t*
                        out);
 }
 
+// ============================ multipoint evaluation and interpolation ==
+// fri_evaluate_ex / fri_interpolate_points_ex on the retained product tree
+// (fri_multipoint.hip).  Evaluation goes down the tree with
+// the vector a_S of a node S (|S| = m words; the coefficients of x^-m..x^-1
+// of f / M_S, lowest power first), interpolation comes up with F_S =
+// sum_{i in S} c_i M_S / (x - x_i).  Both are cyclic products of size m with
+// the children's nodes, whose leading 1 is x^(m/2) = (-1)^k in the transform
+// domain, as in k_roots_pointwise:
+//   down   a_L = (M_R * a_S)[m/2..m),  a_R = (M_L * a_S)[m/2..m)
+//   up     F_S = F_L M_R + F_R M_L
+// a and F are canonical, the tree's nodes Montgomery, so each product of one
+// of each comes out canonical; `scale` is Montgomery(m^-1).
+
+// g = F^-1 mod x^cnt for a series with F[0] = 1 (cnt <= 64, F of lf words):
+// the recurrence g_i = -sum_{j=1..i} F_j g_(i-j) on one lane, the seed of the
+// Newton steps (which would each be four launches on a handful of words).
+__global__ void k_mp_series_seed(const uint32_t* __restrict__ F, uint32_t lf, uint32_t cnt, uint32_t* __restrict__ g) {
+    __shared__ uint32_t gm[64];
+    if (threadIdx.x) return;
+    gm[0] = R_MOD_P;
+    g[0] = 1u;
+    for (uint32_t i = 1; i < cnt; i++) {
+        uint32_t acc = 0;
+        for (uint32_t j = 1; j <= i && j < lf; j++) acc = add(acc, mmul(F[j], gm[i - j]));
+        g[i] = neg(acc);
+        gm[i] = to_mont(neg(acc));
+    }
+}
+void launch_mp_series_seed(const uint32_t* F, size_t lf, uint32_t cnt, uint32_t* g, hipStream_t s) {
+    hipLaunchKernelGGL(k_mp_series_seed, dim3(1), dim3(64), 0, s, F, (uint32_t)(lf < 64 ? lf : 64), cnt, g);
+}
+
+// out[j] = (j + 1) z[j + 1], j < n: the derivative of the monic Z of degree n
+// given by its n low coefficients (z[n] = 1 implied).
+__global__ __launch_bounds__(256) void k_mp_derivative(const uint32_t* __restrict__ z, size_t n,
+                                                       uint32_t* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride)
+        out[j] = mmul(to_mont((uint32_t)(j + 1)), j + 1 < n ? z[j + 1] : 1u);
+}
+void launch_mp_derivative(const uint32_t* z, size_t n, uint32_t* out, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_mp_derivative, dim3(poly_blocks(n)), dim3(256), 0, s, z, n, out);
+}
+
+// Leaf subtrees, evaluation: node S of the leaf level (m = 2^log_leaf points)
+// and its a_S give f(x_i) = sum_u q_i[u] a_S[m-1-u], q_i = M_S / (x - x_i) by
+// the synthetic-division chain of k_lagrange_rows (q[m-1] = 1, q[u-1] =
+// M_S[u] + x_i q[u]).  One lane per point; M_S and a_S are staged in LDS and
+// every lane of a wave reads the same word of each per step (broadcasts).
+// `canon`: the level is the tree's top (one leaf subtree) and holds canonical
+// coefficients.
+__global__ __launch_bounds__(256) void k_mp_leaf_eval(const uint32_t* __restrict__ xs, size_t count,
+                                                      const uint32_t* __restrict__ node, uint32_t canon,
+                                                      const uint32_t* __restrict__ a, uint32_t log_leaf,
+                                                      uint32_t* __restrict__ out) {
+    __shared__ uint32_t Ms[1u << ROOTS_LEAF_LOG_MAX], As[1u << ROOTS_LEAF_LOG_MAX];
+    const uint32_t m = 1u << log_leaf, tid = threadIdx.x;
+    const size_t p0 = (size_t)blockIdx.x * blockDim.x, n0 = (p0 >> log_leaf) << log_leaf;
+    for (uint32_t u = tid; u < m; u += blockDim.x) {
+        const uint32_t v = node[n0 + u];
+        Ms[u] = canon ? to_mont(v) : v;
+        As[u] = a[n0 + u];
+    }
+    __syncthreads();
+    const size_t i = p0 + tid;
+    if (i >= count || i >= n0 + m) return;
+    const uint32_t xm = to_mont(xs[i]);
+    uint32_t q = R_MOD_P, acc = 0;
+    for (uint32_t u = m; u-- > 0;) {
+        acc = add(acc, mmul(q, As[m - 1 - u]));
+        q = add(Ms[u], mmul(q, xm));
+    }
+    out[i] = acc;
+}
+void launch_mp_leaf_eval(const uint32_t* xs, size_t count, const uint32_t* node, bool canon, const uint32_t* a,
+                         uint32_t log_np, uint32_t log_leaf, uint32_t* out, hipStream_t s) {
+    const uint32_t L = 1u << log_leaf, tpb = L < 64 ? 64 : L > 256 ? 256 : L;
+    const size_t np = (size_t)1 << log_np;
+    hipLaunchKernelGGL(k_mp_leaf_eval, dim3((unsigned)((np + tpb - 1) / tpb)), dim3(tpb), 0, s, xs, count, node,
+                       canon ? 1u : 0u, a, log_leaf, out);
+}
+
+// Leaf subtrees, interpolation: k_roots_leaf's scheme with F carried along.
+// Level 0 is M_i = x - x_i, F_i = c_i; a work item owning coefficients k and
+// m + k of a node adds, to the m products of the node itself, the 2m of
+// F_L b + F_R a (M_L = x^m + a, M_R = x^m + b), and m + k also takes
+// F_L[k] + F_R[k].  F uses the layout of the nodes (even nodes in a buffer's
+// first half), so the bank behaviour is the leaf kernel's.  The last level's
+// node is not needed (the tree is retained) and is skipped.  Sums of <= 2^11
+// products stay below 2^43.  LDS: four buffers of 2048 words, 32 KiB.
+__global__ __launch_bounds__(256) void k_mp_leaf_up(const uint32_t* __restrict__ xs, const uint32_t* __restrict__ c,
+                                                    size_t n, uint32_t log_leaf, uint32_t* __restrict__ out) {
+    __shared__ uint32_t buf[2][1u << ROOTS_LEAF_LOG_MAX], fbuf[2][1u << ROOTS_LEAF_LOG_MAX];
+    const uint32_t L = 1u << log_leaf, H = L >> 1, tid = threadIdx.x;
+    const size_t r0 = (size_t)blockIdx.x << log_leaf;
+    for (uint32_t i = tid; i < L; i += blockDim.x) {
+        const bool in = r0 + i < n;
+        const uint32_t pos = log_leaf ? (i & 1u) * H + (i >> 1) : 0u;
+        buf[0][pos] = to_mont(neg(in ? xs[r0 + i] : 0u));
+        fbuf[0][pos] = in ? c[r0 + i] : 0u;
+    }
+    uint32_t cur = 0;
+    for (uint32_t lm = 0; lm < log_leaf; lm++, cur ^= 1u) {
+        const uint32_t m = 1u << lm;
+        const bool last = lm + 1 == log_leaf;
+        const uint32_t* a = buf[cur];
+        const uint32_t* b = buf[cur] + H;
+        const uint32_t* fa = fbuf[cur];
+        const uint32_t* fb = fbuf[cur] + H;
+        __syncthreads();
+        for (uint32_t t = tid; t < H; t += blockDim.x) {
+            const uint32_t nd = t >> lm, k = t & (m - 1);
+            const uint32_t* an = a + nd * m;
+            const uint32_t* bn = b + nd * m;
+            const uint32_t* fan = fa + nd * m;
+            const uint32_t* fbn = fb + nd * m;
+            uint64_t lo = 0, hi = 0, flo = 0, fhi = 0;
+            for (uint32_t i = 0; i < m; i++) {
+                const uint32_t av = an[(k - i) & (m - 1)], bv = bn[(k - i) & (m - 1)];
+                const uint64_t fp = (uint64_t)mmul(fan[i], bv) + mmul(fbn[i], av);
+                flo += i <= k ? fp : 0;
+                fhi += i <= k ? 0 : fp;
+                if (!last) {
+                    const uint64_t p = mmul(an[i], bv);
+                    lo += i <= k ? p : 0;
+                    hi += i <= k ? 0 : p;
+                }
+            }
+            const uint32_t o = last ? 0u : (nd & 1u) * H + (nd >> 1) * 2 * m;
+            fbuf[cur ^ 1u][o + k] = mmul(redc(flo), R2_MOD_P);
+            fbuf[cur ^ 1u][o + m + k] = add(mmul(redc(fhi), R2_MOD_P), add(fan[k], fbn[k]));
+            if (!last) {
+                buf[cur ^ 1u][o + k] = mmul(redc(lo), R2_MOD_P);
+                buf[cur ^ 1u][o + m + k] = add(mmul(redc(hi), R2_MOD_P), add(an[k], bn[k]));
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < L; i += blockDim.x) out[r0 + i] = fbuf[cur][i];
+}
+void launch_mp_leaf_up(const uint32_t* xs, const uint32_t* c, size_t n, uint32_t log_np, uint32_t log_leaf,
+                       uint32_t* out, hipStream_t s) {
+    const uint32_t half = log_leaf ? 1u << (log_leaf - 1) : 1u;
+    const uint32_t tpb = half < 64 ? 64 : half > 256 ? 256 : half;
+    hipLaunchKernelGGL(k_mp_leaf_up, dim3(1u << (log_np - log_leaf)), dim3(tpb), 0, s, xs, c, n, log_leaf, out);
+}
+
+// One level in LDS, products of 2^lg <= 2^ROOTS_LDS_LOG_MAX words, on
+// k_roots_level's tile scheme (a tile of the level is one batched transform).
+// mp_load_child gathers one child (side 0: left) of every node pair of the
+// tile bit-reversed and zero-padded to 2^lg (stage 0 is then the copy).
+__device__ __forceinline__ void mp_load_child(uint32_t* dst, const uint32_t* __restrict__ src, uint32_t tile,
+                                              uint32_t lg, uint32_t side) {
+    const uint32_t h = 1u << (lg - 1);
+    for (uint32_t e = threadIdx.x; e < tile / 2; e += 256) {
+        const uint32_t nb = (e >> (lg - 1)) << lg, i = e & (h - 1);
+        const uint32_t pos = nb + (__brev(i) >> (32 - lg));
+        const uint32_t v = src[nb + side * h + i];
+        dst[pos] = v;
+        dst[pos + 1] = v;
+    }
+}
+constexpr uint32_t MP_TILE_REGS = (1u << ROOTS_LDS_LOG_MAX) / 256;
+// Down: the transform of a_S (all 2^lg words), the two children's, the two
+// middle products, two inverse transforms of which the upper halves are
+// kept: a_L beside a_R, the layout of the tree's level below.
+__global__ __launch_bounds__(256) void k_mp_down_level(const uint32_t* __restrict__ a_in,
+                                                       const uint32_t* __restrict__ nodes, uint32_t* __restrict__ a_out,
+                                                       uint32_t tile, uint32_t lg, const uint32_t* __restrict__ tw_f,
+                                                       const uint32_t* __restrict__ tw_i, uint32_t scale) {
+    __shared__ uint32_t A[1u << ROOTS_LDS_LOG_MAX], B[1u << ROOTS_LDS_LOG_MAX];
+    const uint32_t tid = threadIdx.x, h = 1u << (lg - 1), mask = 2 * h - 1;
+    const size_t base = (size_t)blockIdx.x * tile;
+    for (uint32_t e = tid; e < tile; e += 256) A[(e & ~mask) + (__brev(e & mask) >> (32 - lg))] = a_in[base + e];
+    mp_load_child(B, nodes + base, tile, lg, 1);
+    __syncthreads();
+    roots_stage(A, tile, 0, tw_f);
+    for (uint32_t s = 1; s < lg; s++) {
+        __syncthreads();
+        roots_stage(A, tile, s, tw_f);
+        roots_stage(B, tile, s, tw_f);
+    }
+    __syncthreads();
+    uint32_t pl[MP_TILE_REGS], pr[MP_TILE_REGS];
+#pragma unroll
+    for (uint32_t k = 0; k < MP_TILE_REGS; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e >= tile) continue;
+        pl[k] = mmul(mmul(A[e], add(B[e], (e & 1u) ? P - R_MOD_P : R_MOD_P)), scale);   // a_S (M_R)
+    }
+    __syncthreads();
+    mp_load_child(B, nodes + base, tile, lg, 0);
+    for (uint32_t s = 1; s < lg; s++) {
+        __syncthreads();
+        roots_stage(B, tile, s, tw_f);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < MP_TILE_REGS; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e >= tile) continue;
+        pr[k] = mmul(mmul(A[e], add(B[e], (e & 1u) ? P - R_MOD_P : R_MOD_P)), scale);   // a_S (M_L)
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < MP_TILE_REGS; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e >= tile) continue;
+        const uint32_t pos = (e & ~mask) + (__brev(e & mask) >> (32 - lg));
+        A[pos] = pl[k];
+        B[pos] = pr[k];
+    }
+    for (uint32_t s = 0; s < lg; s++) {
+        __syncthreads();
+        roots_stage(A, tile, s, tw_i);
+        roots_stage(B, tile, s, tw_i);
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < tile; e += 256) {
+        const uint32_t r = e & mask;
+        a_out[base + e] = r < h ? A[e + h] : B[e];
+    }
+}
+void launch_mp_down_level_lds(const uint32_t* a_in, const uint32_t* nodes, uint32_t* a_out, uint32_t log_np,
+                              uint32_t lg, const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s) {
+    const uint32_t tile = log_np < ROOTS_LDS_LOG_MAX ? 1u << log_np : 1u << ROOTS_LDS_LOG_MAX;
+    hipLaunchKernelGGL(k_mp_down_level, dim3((unsigned)(((size_t)1 << log_np) / tile)), dim3(256), 0, s, a_in, nodes,
+                       a_out, tile, lg, tw_fwd, tw_inv, to_mont(inv_std(1u << lg)));
+}
+// Up: F_L with M_R, then F_R with M_L through the same two arrays, the sum
+// held in registers between them; one inverse transform.
+__global__ __launch_bounds__(256) void k_mp_up_level(const uint32_t* __restrict__ f_in,
+                                                     const uint32_t* __restrict__ nodes, uint32_t* __restrict__ f_out,
+                                                     uint32_t tile, uint32_t lg, const uint32_t* __restrict__ tw_f,
+                                                     const uint32_t* __restrict__ tw_i, uint32_t scale) {
+    __shared__ uint32_t A[1u << ROOTS_LDS_LOG_MAX], B[1u << ROOTS_LDS_LOG_MAX];
+    const uint32_t tid = threadIdx.x, mask = (1u << lg) - 1;
+    const size_t base = (size_t)blockIdx.x * tile;
+    uint32_t r[MP_TILE_REGS];
+    for (uint32_t side = 0; side < 2; side++) {
+        if (side) __syncthreads();
+        mp_load_child(A, f_in + base, tile, lg, side);
+        mp_load_child(B, nodes + base, tile, lg, side ^ 1u);
+        for (uint32_t s = 1; s < lg; s++) {
+            __syncthreads();
+            roots_stage(A, tile, s, tw_f);
+            roots_stage(B, tile, s, tw_f);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < MP_TILE_REGS; k++) {
+            const uint32_t e = k * 256 + tid;
+            if (e >= tile) continue;
+            const uint32_t t = mmul(A[e], add(B[e], (e & 1u) ? P - R_MOD_P : R_MOD_P));
+            r[k] = side ? mmul(add(r[k], t), scale) : t;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < MP_TILE_REGS; k++) {
+        const uint32_t e = k * 256 + tid;
+        if (e < tile) A[(e & ~mask) + (__brev(e & mask) >> (32 - lg))] = r[k];
+    }
+    for (uint32_t s = 0; s < lg; s++) {
+        __syncthreads();
+        roots_stage(A, tile, s, tw_i);
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < tile; e += 256) f_out[base + e] = A[e];
+}
+void launch_mp_up_level_lds(const uint32_t* f_in, const uint32_t* nodes, uint32_t* f_out, uint32_t log_np, uint32_t lg,
+                            const uint32_t* tw_fwd, const uint32_t* tw_inv, hipStream_t s) {
+    const uint32_t tile = log_np < ROOTS_LDS_LOG_MAX ? 1u << log_np : 1u << ROOTS_LDS_LOG_MAX;
+    hipLaunchKernelGGL(k_mp_up_level, dim3((unsigned)(((size_t)1 << log_np) / tile)), dim3(256), 0, s, f_in, nodes,
+                       f_out, tile, lg, tw_fwd, tw_inv, to_mont(inv_std(1u << lg)));
+}
+
+// Larger levels: batched NTT passes around these pointwise kernels
+// (elementwise over the level, k mod 2 = word index mod 2).  Down reads the
+// parents' transform ta and the children's tl, tr and leaves ta (M_R) over tr
+// and ta (M_L) over tl; the upper halves of their inverse transforms are the
+// children's vectors, and k_mp_take_high moves a_L's to its place beside a_R.
+__global__ __launch_bounds__(256) void k_mp_down_pointwise(const uint4* __restrict__ ta, uint4* tl, uint4* tr,
+                                                           size_t n4, uint32_t scale) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    auto pw = [&](uint32_t a, uint32_t b, uint32_t sg) { return mmul(mmul(a, add(b, sg)), scale); };
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 a = ta[i], l = tl[i], r = tr[i];
+        uint4 x, y;
+        x.x = pw(a.x, r.x, R_MOD_P);
+        x.y = pw(a.y, r.y, P - R_MOD_P);
+        x.z = pw(a.z, r.z, R_MOD_P);
+        x.w = pw(a.w, r.w, P - R_MOD_P);
+        y.x = pw(a.x, l.x, R_MOD_P);
+        y.y = pw(a.y, l.y, P - R_MOD_P);
+        y.z = pw(a.z, l.z, R_MOD_P);
+        y.w = pw(a.w, l.w, P - R_MOD_P);
+        tr[i] = x;
+        tl[i] = y;
+    }
+}
+void launch_mp_down_pointwise(const uint32_t* ta, uint32_t* tl, uint32_t* tr, size_t words, uint32_t lg,
+                              hipStream_t s) {
+    const uint32_t ninv = inv_std((uint32_t)(((size_t)1 << lg) % P));
+    hipLaunchKernelGGL(k_mp_down_pointwise, dim3(poly_blocks(words / 4)), dim3(256), 0, s,
+                       reinterpret_cast<const uint4*>(ta), reinterpret_cast<uint4*>(tl), reinterpret_cast<uint4*>(tr),
+                       words / 4, to_mont(ninv));
+}
+__global__ __launch_bounds__(256) void k_mp_take_high(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n4,
+                                                      uint32_t lg4) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, h4 = (size_t)1 << (lg4 - 1);
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4 / 2; e += stride) {
+        const size_t o = ((e >> (lg4 - 1)) << lg4) + (e & (h4 - 1));
+        dst[o] = src[o + h4];
+    }
+}
+void launch_mp_take_high(const uint32_t* src, uint32_t* dst, size_t words, uint32_t lg, hipStream_t s) {
+    hipLaunchKernelGGL(k_mp_take_high, dim3(poly_blocks(words / 8)), dim3(256), 0, s,
+                       reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), words / 4, lg - 2);
+}
+// Up: out = (fl (br + s) + fr (bl + s)) / 2^lg; out may be fl.
+__global__ __launch_bounds__(256) void k_mp_up_pointwise(const uint4* fl, const uint4* __restrict__ fr,
+                                                         const uint4* __restrict__ bl, const uint4* __restrict__ br,
+                                                         uint4* out, size_t n4, uint32_t scale) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    auto pw = [&](uint32_t l, uint32_t r, uint32_t ml, uint32_t mr, uint32_t sg) {
+        return mmul(add(mmul(l, add(mr, sg)), mmul(r, add(ml, sg))), scale);
+    };
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 l = fl[i], r = fr[i], ml = bl[i], mr = br[i];
+        uint4 o;
+        o.x = pw(l.x, r.x, ml.x, mr.x, R_MOD_P);
+        o.y = pw(l.y, r.y, ml.y, mr.y, P - R_MOD_P);
+        o.z = pw(l.z, r.z, ml.z, mr.z, R_MOD_P);
+        o.w = pw(l.w, r.w, ml.w, mr.w, P - R_MOD_P);
+        out[i] = o;
+    }
+}
+void launch_mp_up_pointwise(const uint32_t* fl, const uint32_t* fr, const uint32_t* bl, const uint32_t* br,
+                            uint32_t* out, size_t words, uint32_t lg, hipStream_t s) {
+    const uint32_t ninv = inv_std((uint32_t)(((size_t)1 << lg) % P));
+    hipLaunchKernelGGL(k_mp_up_pointwise, dim3(poly_blocks(words / 4)), dim3(256), 0, s,
+                       reinterpret_cast<const uint4*>(fl), reinterpret_cast<const uint4*>(fr),
+                       reinterpret_cast<const uint4*>(bl), reinterpret_cast<const uint4*>(br),
+                       reinterpret_cast<uint4*>(out), words / 4, to_mont(ninv));
+}
+
 }  // namespace fri

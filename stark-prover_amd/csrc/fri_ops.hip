@@ -71,19 +71,15 @@ extern "C" int fri_interpolate(fri_ctx* ctx, const uint32_t* ys, uint32_t log_n,
     return FRI_OK;
 }
 
+// The direct kernels of fri_interpolate_points_ex / fri_evaluate_ex
+// (fri_multipoint.hip validates the arguments and chooses the path).
+namespace fri {
+
 // interpolate_lagrange_polynomials (interpolation.rs:121-152) on arbitrary
 // points: weights, c_j = y_j w_j, f on the 2^k-th roots of unity, iNTT
-// (fri_kernels.hip "arbitrary-point interpolate").
-extern "C" int fri_interpolate_points(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys, size_t n,
-                                      uint32_t* coeffs_out, size_t* len_out) {
-    if (!ctx || !len_out || (n && (!xs || !ys || !coeffs_out))) return fail(ctx, FRI_EINVAL, "null argument");
-    uint32_t log_N = 0;
-    while (((size_t)1 << log_N) < n) log_N++;
-    if (log_N > 17 || log_N > ctx->log_n_max)
-        return fail(ctx, FRI_EINVAL, "arbitrary-point interpolation is O(n^2): n <= 2^17 and <= 2^log_n_max");
-    if (!check_canonical(xs, n) || !check_canonical(ys, n)) return fail(ctx, FRI_EINVAL, "value not canonical (>= p)");
-    *len_out = 0;
-    if (n == 0) return FRI_OK;                                   // Polynomial::zero() (interpolation.rs:133-136)
+// (fri_kernels.hip "arbitrary-point interpolate").  n >= 1, 2^log_N >= n.
+int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* ys, size_t n, uint32_t log_N,
+                              uint32_t* coeffs_out, size_t* len_out) {
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t N = (size_t)1 << log_N;
@@ -106,19 +102,12 @@ extern "C" int fri_interpolate_points(fri_ctx* ctx, const uint32_t* xs, const ui
     FRI_HIP(ctx, hipMemcpyAsync(coeffs_out, ctx->scratch_a, n * 4, hipMemcpyDeviceToHost, s));   // deg f < n
     FRI_HIP(ctx, hipStreamSynchronize(s));
     tmp_trim(ctx);
-    size_t len = n;
-    while (len > 0 && coeffs_out[len - 1] == 0) len--;          // Polynomial::new trim (ops.rs:19-37)
-    *len_out = len;
+    *len_out = trimmed(coeffs_out, n);                           // Polynomial::new trim (ops.rs:19-37)
     return FRI_OK;
 }
 
-extern "C" int fri_evaluate(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count,
-                            uint32_t* out) {
-    if (!ctx || (d && !coeffs) || (count && (!xs || !out))) return fail(ctx, FRI_EINVAL, "null argument");
-    const size_t cap = (size_t)1 << ctx->log_n_max;
-    if (d > cap || count > cap) return fail(ctx, FRI_EINVAL, "size exceeds context capacity");
-    if (!check_canonical(coeffs, d) || !check_canonical(xs, count))
-        return fail(ctx, FRI_EINVAL, "value not canonical (>= p)");
+// Horner at every point (ops.rs:76-83); d, count <= 2^log_n_max.
+int evaluate_direct(fri_ctx* ctx, const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count, uint32_t* out) {
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     if (d) FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_a, coeffs, d * 4, hipMemcpyHostToDevice, ctx->stream));
     if (count) FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_b, xs, count * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -134,6 +123,8 @@ extern "C" int fri_evaluate(fri_ctx* ctx, const uint32_t* coeffs, size_t d, cons
     tmp_trim(ctx);
     return FRI_OK;
 }
+
+}  // namespace fri
 
 extern "C" int fri_fold(fri_ctx* ctx, const uint32_t* layer, uint32_t log_m, uint32_t layer_offset, uint32_t beta,
                         uint32_t* out) {

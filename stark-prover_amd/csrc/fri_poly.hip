@@ -16,43 +16,6 @@ static_assert(FRI_POLY_DIRECT_MAX <= FRI_POLY_DIRECT_LIMIT, "crossover within th
 
 namespace {
 
-size_t trimmed(const uint32_t* v, size_t n) {                     // Polynomial::new (ops.rs:19-37)
-    while (n > 0 && v[n - 1] == 0) n--;
-    return n;
-}
-uint32_t ceil_log2(size_t n) {
-    uint32_t l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
-}
-size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
-
-// dst = NTT_{2^log_N}(src[0..len)), natural order, canonical.
-void forward(fri_ctx* ctx, const uint32_t* src, size_t len, uint32_t log_N, uint32_t* dst) {
-    NttPlan p = lde_plan(ctx, log_N);
-    launch_ntt(p, src, len, dst, ctx->stream);
-}
-// The inverse transform's post-scale N^-1 * R^r_pow: undoes the r_pow factors
-// of R^-1 a pointwise kernel left (fri_kernels.hip "polynomial arithmetic").
-uint32_t post_scale(uint32_t log_N, uint32_t r_pow) {
-    uint32_t scale = inv_std((uint32_t)(((size_t)1 << log_N) % P));
-    for (uint32_t i = 0; i < r_pow; i++) scale = mul_std(scale, R_MOD_P);
-    return scale;
-}
-void inverse_with(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, const uint32_t* post_lo, const uint32_t* post_hi,
-                  uint32_t* dst) {
-    NttPlan p{};
-    p.log_n = log_N;
-    p.tw = ctx->tw_inv;
-    p.post_lo = post_lo;
-    p.post_hi = post_hi;
-    launch_ntt(p, src, (size_t)1 << log_N, dst, ctx->stream);
-}
-// dst = N^-1 * R^r_pow * iNTT(src)
-void inverse(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, uint32_t r_pow, uint32_t* dst) {
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, 1u, post_scale(log_N, r_pow), ctx->stream);
-    inverse_with(ctx, src, log_N, ctx->pow_lo, ctx->pow_hi, dst);
-}
 // The post-scale tables of a division's inverse transforms, made once for the
 // whole call instead of one table launch per transform: every table has base
 // 1, so the low level (Montgomery(1) throughout, ctx->pow_lo) is shared, and a

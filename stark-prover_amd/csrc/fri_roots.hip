@@ -16,17 +16,10 @@ static_assert((FRI_ROOTS_LEAF & (FRI_ROOTS_LEAF - 1)) == 0 && FRI_ROOTS_LEAF >= 
                   FRI_ROOTS_LEAF <= (1 << ROOTS_LEAF_LOG_MAX),
               "FRI_ROOTS_LEAF: a power of two in 128..2048");
 
-namespace {
+namespace fri {
 
-uint32_t ceil_log2(size_t n) {
-    uint32_t l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
-}
-size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
-
-uint32_t leaf_log(const fri_ctx* ctx, uint32_t flags) {
-    if (flags & FRI_ROOTS_SMALL_LEAF) return 6;
+uint32_t roots_leaf_log(const fri_ctx* ctx, bool small_leaf) {
+    if (small_leaf) return 6;
     return ceil_log2(ctx->roots_leaf ? ctx->roots_leaf : FRI_ROOTS_LEAF);
 }
 
@@ -34,19 +27,24 @@ uint32_t leaf_log(const fri_ctx* ctx, uint32_t flags) {
 // to 2^log_np = next_pow2(n) (<= 2^log_n_max); returns where the n low
 // coefficients of Z will be (canonical; the padding's x^pad is skipped).  The
 // levels move between the three context buffers; d_roots is read by the leaf
-// kernel only and may be scratch_b or lie outside them.
-const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, uint32_t lf_log) {
+// kernel only and may be scratch_b or lie outside them.  With `keep`
+// (fri_multipoint.hip) every level stays instead: the level of nodes of degree
+// 2^lg at keep + (lg - lf_log) * 2^log_np, lf_log clamped to log_np, Montgomery
+// but for the canonical top; scratch_a and scratch_b are still work space.
+const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, uint32_t lf_log, uint32_t* keep) {
     hipStream_t s = ctx->stream;
     const uint32_t log_np = ceil_log2(n);
     const size_t np = (size_t)1 << log_np;
     if (lf_log > log_np) lf_log = log_np;
-    uint32_t *cur = ctx->scratch_c, *x = ctx->scratch_a, *y = ctx->scratch_b;
+    uint32_t *cur = keep ? keep : ctx->scratch_c, *x = ctx->scratch_a, *y = ctx->scratch_b;
     launch_roots_leaf(d_roots, n, log_np, lf_log, lf_log == log_np, cur, s);
     for (uint32_t lg = lf_log + 1; lg <= log_np; lg++) {            // nodes of 2^(lg-1) words -> 2^lg
         const bool top = lg == log_np;
+        uint32_t* kept = keep ? keep + (size_t)(lg - lf_log) * np : nullptr;
         if (lg <= ROOTS_LDS_LOG_MAX) {
-            launch_roots_level_lds(cur, x, log_np, lg, top, ctx->tw_fwd, ctx->tw_inv, s);
-            std::swap(cur, x);
+            launch_roots_level_lds(cur, keep ? kept : x, log_np, lg, top, ctx->tw_fwd, ctx->tw_inv, s);
+            if (keep) cur = kept;
+            else std::swap(cur, x);
             continue;
         }
         // even nodes -> x, odd nodes -> y, each zero-padded to 2^lg and
@@ -63,6 +61,7 @@ const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, ui
             launch_ntt(f, cur + off + m, m, y + off, s);
         }
         launch_roots_pointwise(x, y, x, np, lg, top, s);
+        if (keep) cur = kept;
         for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
             const size_t off = p0 << lg;
             NttPlan b{};
@@ -76,7 +75,7 @@ const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, ui
     return cur + (np - n);
 }
 
-}  // namespace
+}  // namespace fri
 
 extern "C" int fri_debug_set_roots_leaf(fri_ctx* ctx, uint32_t leaf) {
     if (!ctx) return FRI_EINVAL;
@@ -100,7 +99,7 @@ extern "C" int fri_poly_from_roots(fri_ctx* ctx, const uint32_t* roots, size_t n
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_b, roots, n * 4, hipMemcpyHostToDevice, s));
-    const uint32_t* z = product_tree(ctx, ctx->scratch_b, n, leaf_log(ctx, flags));
+    const uint32_t* z = product_tree(ctx, ctx->scratch_b, n, roots_leaf_log(ctx, flags & FRI_ROOTS_SMALL_LEAF));
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(out, z, n * 4, hipMemcpyDeviceToHost, s));
     FRI_HIP(ctx, hipStreamSynchronize(s));
@@ -128,7 +127,7 @@ extern "C" int fri_lagrange_basis(fri_ctx* ctx, const uint32_t* xs, size_t n, ui
     FRI_HIP(ctx, hipMemcpyAsync(t + oX, xs, n * 4, hipMemcpyHostToDevice, s));
     launch_interp_weights(t + oX, n, t + oA, t + oT, s);            // prod_{j!=i}(x_i - x_j)
     launch_batch_inverse(t + oA, t + oW, n, 1, s);                  // w_i (Montgomery; 0 -> 0)
-    const uint32_t* z = product_tree(ctx, t + oX, n, leaf_log(ctx, 0));
+    const uint32_t* z = product_tree(ctx, t + oX, n, roots_leaf_log(ctx, false));
     launch_lagrange_rows(t + oX, z, t + oW, n, t + oM, t + oP, s);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(out, t + oM, n * n * 4, hipMemcpyDeviceToHost, s));

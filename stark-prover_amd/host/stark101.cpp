@@ -781,13 +781,31 @@ Poly interpolate(const std::vector<FE>& xs, const std::vector<FE>& ys) {
         auto gpu = Gpu::thread_default(log_n);
         gpu->check(fri_interpolate(gpu->ctx(), y.data(), log_n, static_cast<uint32_t>(offset.value()), c.data(), &len),
                    "fri_interpolate");
-    } else {                                                    // any other point set: O(n^2) on the device
-        auto gpu = Gpu::thread_default(ceil_log2(xs.size()));
+    } else {
+        // any other point set: the product tree from FRI_MP_INTERP_MIN points
+        // (it needs next_pow2(n) <= 2^(log_n_max - 1)), O(n^2) kernels below
+        auto gpu = Gpu::thread_default(ceil_log2(xs.size()) + (xs.size() >= FRI_MP_INTERP_MIN ? 1 : 0));
         auto x = to_u32(xs);
         gpu->check(fri_interpolate_points(gpu->ctx(), x.data(), y.data(), x.size(), c.data(), &len),
                    "fri_interpolate_points");
     }
     return Poly(to_fe(c.data(), len));
+}
+
+std::vector<FE> evaluate_points(const Poly& poly, const std::vector<FE>& xs) {
+    const auto& cf = poly.coefficients;
+    const size_t d = cf.size(), count = xs.size();
+    if (count == 0) return {};
+    // the tree path (min(d, count) >= FRI_MP_EVAL_MIN) needs d + next_pow2(count) - 1
+    // <= 2^log_n_max and next_pow2(d) <= 2^(log_n_max - 1)
+    uint32_t log_n = std::max(ceil_log2(d ? d : 1), ceil_log2(count));
+    if (std::min(d, count) >= FRI_MP_EVAL_MIN)
+        log_n = std::max(ceil_log2(d + ((size_t)1 << ceil_log2(count))), ceil_log2(d) + 1);
+    auto gpu = Gpu::thread_default(log_n);
+    const auto c = to_u32(cf), x = to_u32(xs);
+    std::vector<uint32_t> out(count);
+    gpu->check(fri_evaluate(gpu->ctx(), c.data(), d, x.data(), count, out.data()), "fri_evaluate");
+    return to_fe(out.data(), count);
 }
 
 // ---- Poly arithmetic on the device (ops.rs:114-237) ------------------------

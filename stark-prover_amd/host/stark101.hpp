@@ -585,8 +585,12 @@ bool verify_fibsq(const std::vector<std::vector<uint8_t>>& messages, FE a_last, 
 // evaluate() at every coset point (fri_commit.rs:78): the LDE.
 std::vector<FE> evaluate_on_coset(const Poly& poly, const Coset& coset);
 // Polynomial::interpolate (ops.rs:239-241): the iNTT when xs is a coset
-// offset*<omega_n> in natural order, fri_interpolate_points otherwise.
+// offset*<omega_n> in natural order, fri_interpolate_points otherwise (any n
+// the device holds: the product tree from FRI_MP_INTERP_MIN points).
 Poly interpolate(const std::vector<FE>& xs, const std::vector<FE>& ys);
+// Polynomial::evaluate (ops.rs:76-83) at every x: fri_evaluate (Horner
+// kernels, the product tree from min(len, count) >= FRI_MP_EVAL_MIN).
+std::vector<FE> evaluate_points(const Poly& poly, const std::vector<FE>& xs);
 // Element-wise inverse with inverse(0) = 0 (element.rs:54-57).
 std::vector<FE> batch_inverse(const std::vector<FE>& xs);
 

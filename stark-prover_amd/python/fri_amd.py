@@ -50,6 +50,11 @@ POLY_DIRECT_MAX = 1024    # FRI_POLY_DIRECT_MAX: fri_poly_mul's measured crossov
 ROOTS_SMALL_LEAF = 1      # FRI_ROOTS_SMALL_LEAF: fri_poly_from_roots' test/measurement hook (leaves of 64 roots)
 ROOTS_LEAF = 512          # FRI_ROOTS_LEAF: roots per LDS leaf subtree of the product tree
 LAGRANGE_MAX = 4096       # FRI_LAGRANGE_MAX: fri_lagrange_basis' largest n
+MP_FORCE_TREE = 1         # FRI_MP_FORCE_*: fri_evaluate_ex / fri_interpolate_points_ex test/measurement hooks
+MP_FORCE_DIRECT = 2
+MP_SMALL_LEAF = 4         # FRI_MP_SMALL_LEAF: leaf subtrees of 64 points
+MP_EVAL_MIN = 65536       # FRI_MP_EVAL_MIN: evaluation takes the tree from min(d, count) >= this
+MP_INTERP_MIN = 65536     # FRI_MP_INTERP_MIN: arbitrary-point interpolation takes the tree from n >= this
 
 
 class FriError(RuntimeError):
@@ -117,6 +122,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_interpolate": (i32, [vp, pu32, u32, u32, pu32, ctypes.POINTER(sz)]),
         "fri_interpolate_points": (i32, [vp, pu32, pu32, sz, pu32, ctypes.POINTER(sz)]),
         "fri_evaluate": (i32, [vp, pu32, sz, pu32, sz, pu32]),
+        "fri_evaluate_ex": (i32, [vp, pu32, sz, pu32, sz, u32, pu32]),
+        "fri_interpolate_points_ex": (i32, [vp, pu32, pu32, sz, u32, pu32, ctypes.POINTER(sz)]),
         "fri_poly_mul": (i32, [vp, pu32, sz, pu32, sz, u32, pu32, sz, ctypes.POINTER(sz)]),
         "fri_poly_div_rem": (i32, [vp, pu32, sz, pu32, sz, pu32, sz, ctypes.POINTER(sz), pu32, sz,
                                    ctypes.POINTER(sz)]),
@@ -328,21 +335,31 @@ class Context:
         self._check(self.lib.fri_interpolate(self.h, _ptr(y), log_n, offset, _ptr(out), ctypes.byref(ln)))
         return out[: ln.value]
 
-    def interpolate_points(self, xs, ys) -> np.ndarray:
+    @staticmethod
+    def _mp_flags(mode, small_leaf) -> int:
+        return {None: 0, "tree": MP_FORCE_TREE, "direct": MP_FORCE_DIRECT}[mode] | (MP_SMALL_LEAF if small_leaf else 0)
+
+    def interpolate_points(self, xs, ys, mode: Optional[str] = None, small_leaf: bool = False) -> np.ndarray:
         """Polynomial::interpolate(xs, ys) on arbitrary points
-        (interpolation.rs:121-152; fri_interpolate_points), trimmed."""
+        (interpolation.rs:121-152; fri_interpolate_points_ex), trimmed.
+        mode: None (the measured choice), "tree" or "direct" (the
+        FRI_MP_FORCE_* hooks); small_leaf: the FRI_MP_SMALL_LEAF hook."""
         x, y = _u32(xs), _u32(ys)
         if x.size != y.size:
             raise FriError(FRI_EINVAL, "Mismatched x and y lengths")   # interpolation.rs:127-133 panics
         out = np.empty(max(1, x.size), dtype=np.uint32)
         ln = ctypes.c_size_t()
-        self._check(self.lib.fri_interpolate_points(self.h, _ptr(x), _ptr(y), x.size, _ptr(out), ctypes.byref(ln)))
+        self._check(self.lib.fri_interpolate_points_ex(self.h, _ptr(x), _ptr(y), x.size,
+                                                       self._mp_flags(mode, small_leaf), _ptr(out), ctypes.byref(ln)))
         return out[: ln.value]
 
-    def evaluate(self, coeffs, xs) -> np.ndarray:
+    def evaluate(self, coeffs, xs, mode: Optional[str] = None, small_leaf: bool = False) -> np.ndarray:
+        """Polynomial::evaluate at every x (ops.rs:76-83; fri_evaluate_ex);
+        mode and small_leaf as for interpolate_points."""
         c, x = _u32(coeffs), _u32(xs)
         out = np.empty(x.size, dtype=np.uint32)
-        self._check(self.lib.fri_evaluate(self.h, _ptr(c), c.size, _ptr(x), x.size, _ptr(out)))
+        self._check(self.lib.fri_evaluate_ex(self.h, _ptr(c), c.size, _ptr(x), x.size,
+                                             self._mp_flags(mode, small_leaf), _ptr(out)))
         return out
 
     def poly_mul(self, a, b, force: Optional[str] = None) -> np.ndarray:

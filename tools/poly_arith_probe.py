@@ -19,9 +19,19 @@
       1024 and 4096, beside the device-to-host copy of its n^2 words alone.
       This is the table behind FRI_ROOTS_LEAF (profiles/poly_roots.txt).
 
+
+ (iv) with --multipoint FILE, instead of the above: fri_evaluate_ex with
+      d = count = 2^10 .. 2^20 and fri_interpolate_points_ex with n = 2^10 ..
+      2^20 under FRI_MP_FORCE_DIRECT (as far as the quadratic kernels finish
+      in reasonable time, resp. are accepted) and FRI_MP_FORCE_TREE,
+      alternating, each table twice; and both tree calls at 2^16 for every
+      candidate leaf size.  These are the tables behind FRI_MP_EVAL_MIN and
+      FRI_MP_INTERP_MIN (profiles/poly_multipoint.txt).
+
 Every figure is the median of REPS synchronous C-ABI calls after WARM
 warm-ups, host clock around the call (uploads and read-back included).
-Shapes are seeded.  Usage: poly_arith_probe.py [--out FILE | --roots FILE]"""
+Shapes are seeded.
+Usage: poly_arith_probe.py [--out FILE | --roots FILE | --multipoint FILE]"""
 import argparse
 import ctypes
 import os
@@ -274,22 +284,146 @@ def roots(ctx, corc):
         say("n = %5d  call %9.3f ms   copy %9.3f ms   call - copy %9.3f ms" % (n, t, c, t - c))
 
 
+def mp_eval_call(ctx, c, xs, flags):
+    out = np.empty(xs.size, dtype=np.uint32)
+    pc, px, po = fri_amd._ptr(c), fri_amd._ptr(xs), fri_amd._ptr(out)
+
+    def call():
+        rc = ctx.lib.fri_evaluate_ex(ctx.h, pc, c.size, px, xs.size, flags, po)
+        assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+    return call, out
+
+
+def mp_interp_call(ctx, xs, ys, flags):
+    out = np.empty(xs.size, dtype=np.uint32)
+    ln = ctypes.c_size_t()
+    px, py, po = fri_amd._ptr(xs), fri_amd._ptr(ys), fri_amd._ptr(out)
+
+    def call():
+        rc = ctx.lib.fri_interpolate_points_ex(ctx.h, px, py, xs.size, flags, po, ctypes.byref(ln))
+        assert rc == 0, ctx.lib.fri_last_error(ctx.h)
+    return call, out
+
+
+def alternating_ms(calls):
+    """Medians of the given calls [ms], the candidates alternating."""
+    for c in calls:
+        for _ in range(WARM):
+            c()
+    ts = [[] for _ in calls]
+    for _ in range(REPS):
+        for i, c in enumerate(calls):
+            t0 = time.perf_counter()
+            c()
+            ts[i].append(time.perf_counter() - t0)
+    return [1e3 * statistics.median(t) for t in ts]
+
+
+def distinct_points(seed, n):
+    u = np.unique(fo.splitmix64_np(seed, n + 64))
+    return np.ascontiguousarray(u[np.random.default_rng(seed).permutation(u.size)][:n].astype(np.uint32))
+
+
+MP_EVAL_DIRECT_LOG_MAX = 18      # 2^36 Horner steps; 2^20 would be 2^40
+MP_INTERP_DIRECT_LOG_MAX = 17    # the direct kernels' limit
+
+
+def crossover_from(rows):
+    """The smallest power of two from which the tree is not slower than the
+    direct path (rows: log_n -> (direct, tree), direct None where not run)."""
+    best = None
+    for log_n in sorted(rows, reverse=True):
+        d, t = rows[log_n]
+        if d is not None and t > d:
+            break
+        best = log_n
+    return best
+
+
+def multipoint(ctx):
+    TREE, DIRECT = fri_amd.MP_FORCE_TREE, fri_amd.MP_FORCE_DIRECT
+    cross = {"evaluate": [], "interpolate": []}
+    for run in (1, 2):
+        say("(iv) run %d: fri_evaluate_ex, d = count, whole call [ms, median of %d]" % (run, REPS))
+        say("%8s %12s %12s" % ("d=count", "direct", "tree"))
+        rows = {}
+        for log_n in range(10, 21):
+            n = 1 << log_n
+            c, xs = coeffs(1300 + log_n, n), distinct_points(1400 + log_n, n)
+            tree, got = mp_eval_call(ctx, c, xs, TREE)
+            if log_n <= MP_EVAL_DIRECT_LOG_MAX:
+                direct, want = mp_eval_call(ctx, c, xs, DIRECT)
+                td, tt = alternating_ms([direct, tree])
+                assert np.array_equal(got, want)
+            else:
+                td, tt = None, alternating_ms([tree])[0]
+            rows[log_n] = (td, tt)
+            say("%8s %12s %12.3f" % ("2^%d" % log_n, "%.3f" % td if td is not None else "-", tt))
+        cross["evaluate"].append(crossover_from(rows))
+        say()
+        say("(iv) run %d: fri_interpolate_points_ex, whole call [ms, median of %d]" % (run, REPS))
+        say("%8s %12s %12s" % ("n", "direct", "tree"))
+        rows = {}
+        for log_n in range(10, 21):
+            n = 1 << log_n
+            xs, ys = distinct_points(1500 + log_n, n), coeffs(1600 + log_n, n)
+            tree, got = mp_interp_call(ctx, xs, ys, TREE)
+            if log_n <= MP_INTERP_DIRECT_LOG_MAX:
+                direct, want = mp_interp_call(ctx, xs, ys, DIRECT)
+                td, tt = alternating_ms([direct, tree])
+                assert np.array_equal(got, want)
+            else:
+                td, tt = None, alternating_ms([tree])[0]
+            rows[log_n] = (td, tt)
+            say("%8s %12s %12.3f" % ("2^%d" % log_n, "%.3f" % td if td is not None else "-", tt))
+        cross["interpolate"].append(crossover_from(rows))
+        say()
+    for k in ("evaluate", "interpolate"):
+        say("%s: tree not slower than direct from 2^%s upwards (run 1), 2^%s (run 2)" % (k, *cross[k]))
+    say("FRI_MP_EVAL_MIN, FRI_MP_INTERP_MIN in this build: %d, %d" % (fri_amd.MP_EVAL_MIN, fri_amd.MP_INTERP_MIN))
+    say()
+    say("leaf size at 2^16 (tree paths, fri_debug_set_roots_leaf) [ms, median of %d]" % REPS)
+    say("%12s " % "" + "".join(" %9d" % lf for lf in (64,) + ROOTS_LEAVES))
+    n = 1 << 16
+    c, xs, ys = coeffs(1700, n), distinct_points(1701, n), coeffs(1702, n)
+    for name, call in (("evaluate", mp_eval_call(ctx, c, xs, TREE)[0]),
+                       ("interpolate", mp_interp_call(ctx, xs, ys, TREE)[0])):
+        ts = {lf: [] for lf in (64,) + ROOTS_LEAVES}
+        for lf in ts:
+            ctx.set_roots_leaf(lf)
+            for _ in range(WARM):
+                call()
+        for _ in range(REPS):
+            for lf in ts:
+                ctx.set_roots_leaf(lf)
+                t0 = time.perf_counter()
+                call()
+                ts[lf].append(time.perf_counter() - t0)
+        say("%12s " % name + "".join(" %9.3f" % (1e3 * statistics.median(ts[lf])) for lf in ts))
+    ctx.set_roots_leaf(0)
+    say("FRI_ROOTS_LEAF in this build: %d" % fri_amd.ROOTS_LEAF)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", help="also write the report to this file")
     ap.add_argument("--roots", metavar="FILE", help="run the from_roots / Lagrange section (iii) alone and write it here")
+    ap.add_argument("--multipoint", metavar="FILE",
+                    help="run the multipoint evaluation / interpolation section (iv) alone and write it here")
     args = ap.parse_args()
     ctx = fri_amd.Context(0, LOG_MAX)                              # raises without a gfx950 device
     corc = fo.load_c_oracle()
     corc.orc_set_num_threads(1)
     say("poly_arith_probe: %s, context 2^%d" % (ctx.lib.fri_version().decode(), LOG_MAX))
-    if args.roots:
+    if args.multipoint:
+        multipoint(ctx)
+    elif args.roots:
         roots(ctx, corc)
     else:
         crossover(ctx)
         sizes(ctx, corc)
     ctx.close()
-    out = args.roots or args.out
+    out = args.multipoint or args.roots or args.out
     if out:
         with open(out, "w") as f:
             f.write("\n".join(_lines) + "\n")
