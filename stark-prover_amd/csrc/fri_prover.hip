@@ -47,7 +47,10 @@ __global__ __launch_bounds__(256) void k_fibsq_cp(const uint32_t* __restrict__ f
     for (int k = CP_K - 1; k >= 0; k--) {
         const uint32_t dinv = mmul(inv, pre[k]);           // 1 / ((x-1)(x-g^{T-1}))
         inv = mmul(inv, mmul(xa[k], xb[k]));
-        const size_t i = i0 + k;
+        // n = 8 (log_t 2, blowup 2) is less than one lane's CP_K points: lane 0's
+        // points 8..15 are points 0..7 again (w^n = 1), so the wrapped index reads
+        // and writes the same words with the same values, inside the n-word buffers
+        const size_t i = (i0 + k) & mask;
         const uint32_t fi = f[i], f1 = f[(i + q.B) & mask], f2 = f[(i + 2 * q.B) & mask];
         const uint32_t p0 = mmul(sub(fi, 1u), mmul(dinv, xb[k]));        // (f-1)/(x-1)
         const uint32_t p1 = mmul(sub(fi, q.a_last), mmul(dinv, xa[k]));  // (f-A)/(x-g^{T-1})
