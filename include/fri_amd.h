@@ -441,6 +441,90 @@ int fri_ctx_set_lanes(fri_ctx* ctx, uint32_t max_lanes);
  * FRI_EINVAL for a ticket that is not pending. */
 int fri_debug_ticket_lane(fri_ctx* ctx, uint64_t ticket, int* lane);
 
+/* Batched commit: `batch` independent fri_commit calls (src/fri/fri_commit.rs:
+ * 72-122) of one shape in one call, for the many small codewords of
+ * per-transaction proofs and recursion leaves, whose single commits are a
+ * serial chain of one-workgroup launches on an otherwise idle chip.
+ * Member b: coefficients coeffs + b*d (d each, trailing zeros allowed), channel
+ * chan_in[b] (chan_in NULL: every member starts from Channel::new()), forced
+ * betas forced_betas + b*FRI_MAX_ROUNDS (with FRI_FLAG_FORCE_BETAS), result
+ * out[b], status[b].  out[b] is word for word what fri_commit returns for the
+ * same arguments, and the member's stored layers, tree levels, degrees and
+ * decommitments (fri_batch_*) are what the single commit's read-backs return.
+ *
+ * How it runs: the LDE of all members is a fixed number of launches, in LDS
+ * (one workgroup per member) for log_n <= FRI_BATCH_LDE_LDS_MAX_LOG_N and as
+ * one pointwise launch plus the batched transform above it; then ONE launch
+ * commits every member, one 512-thread workgroup each, from layer 0 to its
+ * last layer (layers above 2^9 elements in tiles of 2^9 leaves through the
+ * member's HBM slots, smaller ones in LDS).  No workgroup ever waits for
+ * another.  One CU hashes a whole member, so a small batch is slower than a
+ * loop of fri_commit_device: batch where there are tens of members or more
+ * (the table below).
+ *
+ * 1 <= log_n <= FRI_BATCH_MAX_LOG_N (and the context's log_n_max), d <= 2^log_n
+ * (else FRI_EDEGREE), 1 <= batch <= 65535.  Flags: FRI_FLAG_FORCE_BETAS, and
+ * FRI_FLAG_NO_GRAPH (accepted, no effect: a batch replays no graph); any other
+ * is FRI_EINVAL.  A multi-GPU context gives FRI_EINVAL, a profiling context
+ * FRI_ESTATE.  Argument errors write nothing.  The call first waits for
+ * pending pipelined commits.  A member with a coefficient >= p (found on the
+ * device) gets status[b] = FRI_EINVAL and serves no read-backs (FRI_ESTATE);
+ * every other member is served.  The call returns FRI_OK when every member
+ * succeeded, else the first failing member's code.
+ *
+ * Memory per member: the one-GPU plan's layers and trees,
+ *   4 * (2^(log_n+1) - 2^(log_n-R)) + 32 * sum_{k<=R} (2^(log_n-k+1) - 1) bytes
+ * (R = the rounds bound of d: ceil(log2 d), at most log_n), two coefficient
+ * buffers of 4 * (d/2 + 1) bytes, 4 * d more for host input and 4 * d more
+ * above FRI_BATCH_LDE_LDS_MAX_LOG_N, and a 2.2 KB state: 8.6 MiB at 2^16 with
+ * d = 2^13.  The x^-1, power and twiddle tables are shared by the members.
+ * The buffers belong to the batch, grow on demand and stay until a larger
+ * batch or fri_ctx_destroy; no single commit's plan or graph is touched.
+ * FRI_ENOMEM leaves the context usable and what was resident readable.
+ *
+ * Residency: a batch bumps the commit generation; after it fri_commit_info
+ * reports n_layers = 0 and the single-commit read-backs give FRI_ESTATE
+ * (their message names fri_batch_*); after any later commit the fri_batch_*
+ * read-backs give FRI_ESTATE.
+ *
+ * FRI_BATCH_MAX_LOG_N: the largest measured log_n in 14..18 at which a batch
+ * of 256 is faster per commit than three pipelined commits pending
+ * (tools/batch_probe.py, profiles/commit_batch.txt; us per commit, d = n/8):
+ *   log_n   loop of fri_commit_device   3 pipelined pending   batch of 16     64    256   1024
+ *     8              225                     79                   14.4    3.9    1.3    0.9
+ *    10              329                    115                   23.3    6.1    1.8    1.3
+ *    12              445                    155                   54.6   14.1    3.9    2.7
+ *    14              570                    203                    171   43.3   11.2    8.2
+ *    16              710                    264                    627    157   40.1   29.7
+ *    18              911                    359                   2440    614    156      -
+ * A batch of 1 costs 215 us at 2^8 and 38.9 ms at 2^18 (one CU hashes the whole
+ * member): a batch beats the loop from 16 members on (64 at 2^18), the
+ * pipelined commits from 16 up to 2^14, 64 at 2^16 and 256 at 2^18.  At 256
+ * members it is 63x (2^10) to 2.3x (2^18) faster per commit than three
+ * pipelined commits, so the cap is 18.  The first call of a shape also
+ * allocates: 0.9 ms (2^10, B = 256) to 41 ms (2^18, B = 256) in all.
+ */
+#define FRI_BATCH_MAX_LOG_N          18
+#define FRI_BATCH_LDE_LDS_MAX_LOG_N  12
+int fri_commit_batch(fri_ctx* ctx, const uint32_t* coeffs, size_t d, uint32_t batch, uint32_t log_n,
+                     uint32_t offset, const fri_channel_state* chan_in, uint32_t flags,
+                     const uint32_t* forced_betas, fri_commit_result* out, int* status);
+/* Same, d_coeffs a device pointer to batch*d words, read in place. */
+int fri_commit_batch_device(fri_ctx* ctx, const uint32_t* d_coeffs, size_t d, uint32_t batch, uint32_t log_n,
+                            uint32_t offset, const fri_channel_state* chan_in, uint32_t flags,
+                            const uint32_t* forced_betas, fri_commit_result* out, int* status);
+/* The resident batch: the commit generation, its members and log_n (batch = 0:
+ * the last commit call was not a batch). */
+int fri_batch_info(fri_ctx* ctx, uint64_t* generation, uint32_t* batch, uint32_t* log_n);
+/* fri_layer_copy, fri_tree_level_copy, fri_commit_degrees and
+ * fri_decommit_query of one member of the resident batch. */
+int fri_batch_layer_copy(fri_ctx* ctx, uint32_t member, uint32_t layer, uint32_t* out, size_t cap);
+int fri_batch_tree_level_copy(fri_ctx* ctx, uint32_t member, uint32_t layer, uint32_t level, uint8_t* out,
+                              size_t cap);
+int fri_batch_commit_degrees(fri_ctx* ctx, uint32_t member, int32_t* out, size_t cap, uint32_t* n_out);
+int fri_batch_decommit_query(fri_ctx* ctx, uint32_t member, uint64_t index, uint32_t* values, size_t values_cap,
+                             uint8_t* paths, size_t paths_cap, size_t* paths_len);
+
 /* Which commit the read-backs below serve: `generation` grows with every
  * commit call on the context (successful or not), log_n / n_layers describe
  * the resident commit (n_layers = 0 when the last commit failed).  A binding

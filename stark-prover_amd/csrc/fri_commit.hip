@@ -199,8 +199,13 @@ void fri::init_state(fri_ctx* ctx, DevState* h, const fri_channel_state* chan_in
                        const uint32_t* forced_betas) {
     ctx->h_state = h;
     ctx->res_lane = ctx->cur_lane;
-    memset(h, 0, sizeof(DevState));      // n_layers = 0: nothing readable until this commit succeeds
+    ctx->batch.resident = false;         // the fri_batch_* read-backs serve a batch only while it is the last commit
     ctx->commit_gen++;
+    state_reset(h, chan_in, flags, forced_betas);
+}
+// The DevState a commit (or a member of a batch) starts from.
+void fri::state_reset(DevState* h, const fri_channel_state* chan_in, uint32_t flags, const uint32_t* forced_betas) {
+    memset(h, 0, sizeof(DevState));      // n_layers = 0: nothing readable until this commit succeeds
     if (chan_in && chan_in->has_state) {
         for (int i = 0; i < 8; i++)
             h->chan[i] = ((uint32_t)chan_in->digest[4 * i] << 24) | ((uint32_t)chan_in->digest[4 * i + 1] << 16) |

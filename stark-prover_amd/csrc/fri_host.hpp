@@ -9,6 +9,8 @@
 //   fri_multipoint.hip evaluation and interpolation at arbitrary points, on the tree
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
+//   fri_batch.hip      the batched commit of many small codewords and its
+//                      member-wise read-backs
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
 //                      which commit the read-backs serve (residency)
 //   fri_readback.hip   read-backs, decommitment and the prover entry points
@@ -107,6 +109,36 @@ struct Lane {
     Plan plan;
     hipStream_t stream = nullptr;
     DevState* d_state = nullptr;
+};
+
+// The batched commit (fri_commit_batch, fri_batch.hip): its own buffers, one
+// slice per member (laid out like a one-GPU plan, Batch::lay), grown on demand
+// and kept until a larger batch or fri_ctx_destroy; no lane's plan is touched.
+enum {
+    BB_LAYERS, BB_TREES, BB_COEFA, BB_COEFB,
+    BB_IN,        // staged input (host coefficients)
+    BB_SCALED,    // c_j offset^j, the batched transform's input
+    BB_STATES,    // one DevState per member
+    BB_N
+};
+struct BatchBufs {
+    void* dev[BB_N] = {};
+    size_t cap[BB_N] = {};          // bytes
+    DevState* h_states = nullptr;   // pinned: the members' states in and out
+    size_t h_cap = 0;               // members
+    uint32_t* words(int i) const { return static_cast<uint32_t*>(dev[i]); }
+};
+struct Batch {
+    bool resident = false;       // the last commit call on the context was a batch
+    uint32_t count = 0, log_n = 0;
+    Plan lay;                    // a member's layout (offsets only; no buffers, never `valid`)
+    size_t lay_stride = 0, tre_stride = 0, coef_stride = 0;
+    BatchBufs b;
+    // shared by the members (same log_n and offset): x^-1 of every fold, the pre-scale power table
+    uint32_t* xinv = nullptr;
+    uint32_t* pre_lo = nullptr;
+    uint32_t* pre_hi = nullptr;
+    uint32_t tab_log_n = 0, tab_offset = 0;
 };
 
 struct Team;   // in-process team (defined below)
@@ -247,6 +279,7 @@ struct fri_ctx {
     uint32_t sharded_layers = 0;    // layers of the last commit held block-wise across ranks
     uint64_t commit_gen = 0;        // bumped by every commit: read-backs of an older proof are refused
     uint32_t commit_log_n = 0;      // codeword log2 of the resident commit
+    Batch batch;                    // fri_commit_batch: buffers and residency (fri_batch.hip)
     uint32_t* interp_tmp = nullptr; // partials of fri_interpolate_points / fri_evaluate, fri_merkle_root's tree (grown on use)
     size_t interp_cap = 0;
     uint32_t roots_leaf = 0;        // fri_debug_set_roots_leaf: roots per leaf subtree (0: FRI_ROOTS_LEAF)
@@ -478,6 +511,7 @@ void plan_layout(Plan& p, size_t d, uint32_t log_n, uint32_t G, uint32_t rank, s
 int plan_build(fri_ctx* ctx, size_t d, uint32_t log_n, uint32_t offset, uint32_t G = 1, uint32_t rank = 0);
 uint32_t* coef_buf(Plan& p, int r);
 LayerTask commit_task(fri_ctx* ctx, int k);
+void state_reset(DevState* h, const fri_channel_state* chan_in, uint32_t flags, const uint32_t* forced_betas);
 void init_state(fri_ctx* ctx, DevState* h, const fri_channel_state* chan_in, uint32_t flags,
                 const uint32_t* forced_betas);
 int commit_validate(fri_ctx* ctx, size_t d, uint32_t log_n, uint32_t offset, uint32_t flags,
@@ -503,6 +537,11 @@ int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* 
 
 // ---- fri_readback.hip
 int dq_alloc(fri_ctx* ctx);                   // pinned host buffer the gather kernels write
+// FRI_ESTATE of a single-commit read-back that finds no such layer
+int no_layer(fri_ctx* ctx, const char* what);
+
+// ---- fri_batch.hip
+void batch_free(fri_ctx* ctx);                // fri_ctx_destroy
 
 int input_checksum(fri_ctx* ctx, const uint32_t* d_src, size_t d, uint64_t* out);   // (synchronous)
 

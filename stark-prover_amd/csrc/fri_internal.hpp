@@ -271,6 +271,36 @@ void launch_replicate(const uint32_t* src, uint32_t* dst, size_t words, uint32_t
 // nodes, <= 512) is already in t.tree; mx/G: coefficient maxima.
 void launch_top(const LayerTask& t, uint32_t l, const int32_t* mx, uint32_t G, hipStream_t s);
 
+// Batched commit (fri_commit_batch; k_commit_batch, fri_layer.hip): `batch`
+// independent commits of one shape, one 512-thread workgroup each.  Member b
+// owns the slice b of every buffer (layers + b * lay_stride, ...), laid out
+// inside like a one-GPU plan (layer_off / tree_off, in words); the x^-1 tables
+// are shared (fold k reads xinv + xinv_off[k]).  st: one DevState per member.
+constexpr uint32_t BATCH_MAX_LOG = 18;   // tiles of 2^9 leaves, <= 2^9 tile roots
+constexpr uint32_t BATCH_LDS_LDE_MAX_LOG = 12;   // LDE in LDS up to here, NttPlan::batch above
+struct BatchTask {
+    uint32_t* layers;
+    uint32_t* trees;
+    uint32_t* coefA;           // poly_k of odd k (layers above 2^TAIL_LOG only: smaller ones stay in LDS)
+    uint32_t* coefB;           // poly_k of even k >= 2
+    const uint32_t* coef_in;   // member b's d0 input coefficients at coef_in + b * in_stride
+    const uint32_t* xinv;
+    DevState* st;
+    size_t lay_stride, tre_stride, coef_stride, in_stride;
+    uint32_t log_n, d0;
+    int rmax;
+    uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2], xinv_off[BATCH_MAX_LOG + 2];
+};
+void launch_commit_batch(const BatchTask& bt, uint32_t batch, hipStream_t s);
+// LDE of every member, layer 0 := the member's coefficients on offset * <w_n>.
+// dst[b * dst_stride + j] = src[b * src_stride + j] * offset^j, j < d (lo / hi: launch_pow_table)
+void launch_batch_scale(const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride, size_t d,
+                        uint32_t batch, const uint32_t* lo, const uint32_t* hi, hipStream_t s);
+// log_n <= BATCH_LDS_LDE_MAX_LOG: scale and transform in LDS, one workgroup per member
+void launch_batch_lde_lds(const uint32_t* src, size_t src_stride, size_t d, uint32_t* layers, size_t lay_stride,
+                          uint32_t log_n, uint32_t batch, const uint32_t* tw, const uint32_t* lo, const uint32_t* hi,
+                          hipStream_t s);
+
 // fri_prover.hip — STARK-101 FibonacciSq composition on the LDE coset.
 constexpr uint32_t FIBSQ_MAX_B = 16;   // blowup <= 2^4
 struct FibsqParams {

@@ -18,6 +18,8 @@
 //   k_tree_tail   (ONE workgroup, ONE launch): all of a commit's layers of
 //       <= 2^9 elements, each one whole (fold, leaves, levels, coefficient
 //       fold, channel step).
+//   k_commit_batch (fri_commit_batch: one workgroup per member of a batch):
+//       a member's whole commit from layer 0, larger layers in tiles of 2^9.
 //
 // Each thread of k_layer_leaf takes 4 consecutive leaves and folds them to one
 // level-2 node in registers (no LDS, no barrier, no idle lanes); levels 3 / 4
@@ -1057,6 +1059,262 @@ __global__ __launch_bounds__(512) void k_tree_tail(TailTask tt) {
         beta_m = s_beta_m;
         prev_deg = s_deg;
     }
+}
+
+// ------------------------------------------------------------ batch ----
+// fri_commit_batch: member blockIdx.x's whole commit in ONE workgroup of ONE
+// launch: k_tree_tail generalised to start at layer 0 of a codeword of up to
+// 2^BATCH_MAX_LOG elements.  Per layer, as in the tail: fold, leaves, tree,
+// coefficient fold, degree, channel step, beta; the loop ends (uniformly per
+// workgroup) when the member's degree drops below 1, so members of one batch
+// end at different layers.
+//   L <= TAIL_LOG: the tail's LDS path (values and coefficients of the
+//       previous layer in LDS, whole tree in one level loop).
+//   L >  TAIL_LOG: tiles of 2^TAIL_LOG leaves: fold, store, hash, climb nine
+//       levels in LDS; then the level loop runs over the 2^(L - TAIL_LOG) tile
+//       roots.  Values, coefficients and digests of these layers go through
+//       the member's own slots in HBM.
+// Producer and consumer of every such word are this workgroup, so a
+// workgroup barrier is the only synchronisation: nothing here waits for
+// another workgroup (no flag, no atomic, no cooperative launch), whatever the
+// batch size and however the workgroups are scheduled.
+__global__ __launch_bounds__(512) void k_commit_batch(BatchTask bt) {
+    constexpr uint32_t NMAX = 1u << TAIL_LOG;
+    __shared__ uint4 lds[2 * NMAX + NMAX];
+    __shared__ uint32_t vals[2][NMAX];         // this / previous layer's values (layers of <= NMAX)
+    __shared__ uint32_t coefs[2][NMAX];        // this / previous round's polynomial (the same layers)
+    __shared__ int32_t red[24];
+    __shared__ uint32_t s_beta_m, s_active;
+    __shared__ int32_t s_deg;
+    __shared__ uint32_t s_fbeta[BATCH_MAX_LOG + 2];   // the test hook's betas (layer_results' fbeta1), by layer
+    __shared__ SchedLds sl;
+    sched_init(&sl);
+    uint32_t ord = 0;                            // levels so far (schedule producer flag)
+    const uint32_t tid = threadIdx.x;
+    const bool chan_wave = tid >= 448;
+    const size_t mb = blockIdx.x;
+    DevState* st = bt.st + mb;
+    uint32_t* layers = bt.layers + mb * bt.lay_stride;
+    uint32_t* trees = bt.trees + mb * bt.tre_stride;
+    const uint32_t* input = bt.coef_in + mb * bt.in_stride;
+    uint32_t* cA = bt.coefA + mb * bt.coef_stride;
+    uint32_t* cB = bt.coefB + mb * bt.coef_stride;
+    auto cbuf = [&](int r) -> uint32_t* { return (r & 1) ? cA : cB; };   // poly_r, r >= 1 (fri::coef_buf)
+    uint32_t cs[8], X[4];
+    uint32_t has = 0;
+    if (chan_wave) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) cs[i] = st->chan[i];
+        has = st->chan_has;
+    }
+    uint32_t pending = chan_wave ? st->chan_pending : 0u;
+    if (tid >= 384 && tid < 448) kcache_touch_sha_tables();
+    if (tid < (uint32_t)bt.rmax + 2)
+        s_fbeta[tid] = (st->forced && tid < (uint32_t)MAXR) ? st->forced_beta[tid] + 1u : 0u;   // +1: 0 means not forced
+    uint32_t beta_m = 0u;
+    int prev_deg = -1;
+    const shaq::Role R = shaq::role_of(tid);
+#pragma unroll 1
+    for (int k = 0; k <= bt.rmax; k++) {
+        const uint32_t L = bt.log_n - (uint32_t)k, N = 1u << L;
+        LayerTask t{};                           // what the shared helpers read of it
+        t.st = st;
+        t.k = k;
+        t.L = L;
+        const bool big = L > TAIL_LOG;
+        const bool prev_lds = k > 0 && L + 1 <= TAIL_LOG;    // layer k-1 ran the LDS path
+        const bool coef_lds = k >= 2 && prev_lds;            // ... and folded poly_{k-1} there
+        const uint32_t* xl = k ? bt.xinv + bt.xinv_off[k - 1] : nullptr;
+        const uint32_t* prev = k ? layers + bt.layer_off[k - 1] : nullptr;
+        uint32_t* values = layers + bt.layer_off[k];
+        uint32_t* tr = trees + bt.tree_off[k];
+        uint32_t* cur_v = vals[k & 1];
+        const uint32_t* prev_v = vals[(k & 1) ^ 1];
+        uint32_t* cur_c = coefs[k & 1];
+        const uint32_t* prev_c = coefs[(k & 1) ^ 1];
+        uint4* A = lds;
+        uint4* B = lds + 2 * NMAX;
+        // ---- coefficient fold of round k-1 (or the input scan at k == 0), all waves ----
+        {
+            Mx3 m;
+            if (k == 0) {
+                for (uint32_t j = tid; j < bt.d0; j += blockDim.x) {
+                    const uint32_t c = input[j];
+                    if (c) m.m0 = max(m.m0, (int)j);
+                    if (c >= P) m.m1 = 0;                  // not canonical (see Mx3)
+                }
+            } else {
+                const uint32_t len = (uint32_t)(prev_deg + 1), nlen = (len + 1) / 2;
+                const uint32_t* cin = coef_lds ? prev_c : (k == 1 ? input : cbuf(k - 1));
+                uint32_t* cout = big ? cbuf(k) : cur_c;
+                for (uint32_t j = tid; j < nlen; j += blockDim.x) {
+                    const uint32_t e = cin[2 * j];
+                    const uint32_t o = (2 * j + 1 < len) ? cin[2 * j + 1] : 0u;
+                    const uint32_t v = add(e, mmul(o, beta_m));
+                    cout[j] = v;
+                    if (v) m.m0 = (int)j;
+                    if (e) m.m1 = (int)j;
+                    if (o) m.m2 = (int)j;
+                }
+            }
+            mx3_wave_to_red(m, red, tid);
+        }
+        // ---- fold + leaves (+ the tiles' nine levels): N2 digests of level lvl0 in A ----
+        uint32_t N2 = N, lvl0 = 0;
+        if (big) {
+            const uint32_t tiles = N >> TAIL_LOG;
+#pragma unroll 1
+            for (uint32_t tile = 0; tile < tiles; tile++) {
+                A = lds;
+                B = lds + 2 * NMAX;
+                const uint32_t i = (tile << TAIL_LOG) + tid;
+                uint32_t v;
+                if (k) {
+                    v = fold_one(prev[i], prev[i + N], xl[i], beta_m);
+                    values[i] = v;
+                } else {
+                    v = values[i];
+                }
+                Dg d;
+                cleaf(v, d);
+                dg_store(tr + 8 * (size_t)i, d);
+                dg_lds_store(A + 2 * tid, d);
+                lds_barrier();
+                uint32_t cnt = NMAX;
+#pragma unroll 1
+                for (uint32_t j = 1; j <= TAIL_LOG; j++) {
+                    cnt >>= 1;
+                    level_step(t, false, 0, A, B, tr + 8 * (level_offset(L, j) + ((size_t)tile << (TAIL_LOG - j))), cnt,
+                               R, &sl, ord++);
+                    lds_barrier();
+                    uint4* tmp = A; A = B; B = tmp;
+                }
+            }
+            // the tile roots (and this layer's values and coefficients), written by this workgroup
+            __syncthreads();
+            N2 = tiles;
+            lvl0 = TAIL_LOG;
+            A = lds;
+            B = lds + 2 * NMAX;
+            const uint32_t* in = tr + 8 * level_offset(L, TAIL_LOG);
+            for (uint32_t i = tid; i < N2; i += blockDim.x) {
+                Dg d;
+                dg_load(in + 8 * i, d);
+                dg_lds_store(A + 2 * i, d);
+            }
+        } else {
+            leaf_loop(N, tr, A, [&](uint32_t j, bool real) {
+                uint32_t v;
+                if (k) {
+                    const uint32_t a = prev_lds ? prev_v[j] : prev[j], b = prev_lds ? prev_v[j + N] : prev[j + N];
+                    v = fold_one(a, b, xl[j], beta_m);
+                    if (real) values[j] = v;
+                } else {
+                    v = values[j];
+                }
+                if (real) cur_v[j] = v;
+                return v;
+            });
+        }
+        lds_barrier();
+        // ---- degree of poly_k, uniform: is this the member's last layer? ----
+        const Degree dg = degree_of(k, mx3_from_red(red, 8));
+        const int job_end = dg.deg < 1 ? CJ_END_FINAL : CJ_END_ROUND;
+        uint32_t fv = 0;                               // fri_commit.rs:109-113
+        if (chan_wave && dg.deg == 0) fv = (k == 0) ? input[0] : (big ? cbuf(k)[0] : cur_c[0]);
+        // ---- levels + channel jobs ----
+        int job = CJ_END_FINAL;
+        if (chan_wave) job = !has ? CJ_ROOT : (pending ? CJ_REHASH : CJ_MID);
+        const uint32_t nlev = L - lvl0;
+        const uint32_t total = nlev + 1;               // the levels, then wave 7's remaining channel jobs
+        uint32_t cnt = N2;
+#pragma unroll 1
+        for (uint32_t it = 0; it < total; it++) {
+            const bool level = it < nlev;
+            if (level) {
+                cnt >>= 1;
+                level_step(t, false, it, A, B, tr + 8 * level_offset(L, lvl0 + 1 + it), cnt, R, &sl, ord++);
+            }
+            if (chan_wave) job = chan_drain(t, job, job_end, level, cnt, cs, X, has, A, fv, R);
+            lds_barrier();
+            if (level) {
+                uint4* tmp = A; A = B; B = tmp;
+            }
+        }
+        // ---- results (one lane of wave 7), hand-off to the next layer ----
+        if (tid == 448) {
+            const RoundOut r = layer_results(t, dg, cs, fv, s_fbeta[k], A);
+            s_beta_m = r.beta_m;
+            s_active = r.active;
+            s_deg = dg.deg;
+        }
+        if (chan_wave) { has = 1; pending = 1; }
+        __syncthreads();                                 // (also this layer's values in HBM: the next fold reads them)
+        if (!s_active) break;                            // uniform
+        beta_m = s_beta_m;
+        prev_deg = s_deg;
+    }
+}
+
+void launch_commit_batch(const BatchTask& bt, uint32_t batch, hipStream_t s) {
+    assert(bt.log_n >= 1 && bt.log_n <= BATCH_MAX_LOG && bt.rmax <= (int)bt.log_n);
+    hipLaunchKernelGGL(k_commit_batch, dim3(batch), dim3(512), 0, s, bt);
+}
+
+// The members' LDE.  Pointwise c_j * offset^j, for the batched transform
+// (NttPlan::batch takes no pre-scale table) ...
+__global__ __launch_bounds__(256) void k_batch_scale(const uint32_t* __restrict__ src, size_t src_stride,
+                                                     uint32_t* __restrict__ dst, size_t dst_stride, size_t d,
+                                                     const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= d) return;
+    const uint32_t v = src[blockIdx.y * src_stride + j];
+    dst[blockIdx.y * dst_stride + j] = mmul(mmul(v, hi[j >> POW_LO_LOG]), lo[j & ((1u << POW_LO_LOG) - 1)]);
+}
+void launch_batch_scale(const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride, size_t d,
+                        uint32_t batch, const uint32_t* lo, const uint32_t* hi, hipStream_t s) {
+    if (!d) return;
+    hipLaunchKernelGGL(k_batch_scale, dim3((unsigned)((d + 255) / 256), batch), dim3(256), 0, s, src, src_stride, dst,
+                       dst_stride, d, lo, hi);
+}
+
+// ... and, for transforms of <= 2^BATCH_LDS_LDE_MAX_LOG points (below the
+// batched transform's whole tiles), scale and a radix-2 DIT in LDS, one
+// workgroup per member: bit-reversed load, stage s with tw[2^s + j]
+// (launch_twiddles), natural-order canonical output into the member's layer 0.
+__global__ __launch_bounds__(256) void k_batch_lde_lds(const uint32_t* __restrict__ src, size_t src_stride, uint32_t d,
+                                                       uint32_t* __restrict__ layers, size_t lay_stride, uint32_t log_n,
+                                                       const uint32_t* __restrict__ tw, const uint32_t* __restrict__ lo,
+                                                       const uint32_t* __restrict__ hi) {
+    __shared__ uint32_t a[1u << BATCH_LDS_LDE_MAX_LOG];
+    const uint32_t n = 1u << log_n;
+    const uint32_t* in = src + blockIdx.x * src_stride;
+    uint32_t* out = layers + blockIdx.x * lay_stride;
+    for (uint32_t j = threadIdx.x; j < n; j += 256) {
+        uint32_t v = 0u;
+        if (j < d) v = mmul(mmul(in[j], hi[j >> POW_LO_LOG]), lo[j & ((1u << POW_LO_LOG) - 1)]);
+        a[__brev(j) >> (32 - log_n)] = v;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s = 0; s < log_n; s++) {
+        const uint32_t half = 1u << s;
+        for (uint32_t idx = threadIdx.x; idx < n / 2; idx += 256) {
+            const uint32_t j = idx & (half - 1), p0 = ((idx >> s) << (s + 1)) + j;
+            const uint32_t u = a[p0], w = mmul(a[p0 + half], tw[half + j]);
+            a[p0] = add(u, w);
+            a[p0 + half] = sub(u, w);
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = threadIdx.x; j < n; j += 256) out[j] = a[j];
+}
+void launch_batch_lde_lds(const uint32_t* src, size_t src_stride, size_t d, uint32_t* layers, size_t lay_stride,
+                          uint32_t log_n, uint32_t batch, const uint32_t* tw, const uint32_t* lo, const uint32_t* hi,
+                          hipStream_t s) {
+    assert(log_n >= 1 && log_n <= BATCH_LDS_LDE_MAX_LOG && d <= ((size_t)1 << log_n));
+    hipLaunchKernelGGL(k_batch_lde_lds, dim3(batch), dim3(256), 0, s, src, src_stride, (uint32_t)d, layers, lay_stride,
+                       log_n, tw, lo, hi);
 }
 
 // ------------------------------------------------------------ launcher ----

@@ -5,11 +5,18 @@
 // commit, trace decommitment).
 #include "fri_host.hpp"
 
+// After fri_commit_batch the context holds the members' proofs, not a single
+// commit's: the single-commit read-backs refuse and say where to look.
+int fri::no_layer(fri_ctx* ctx, const char* what) {
+    return fail(ctx, FRI_ESTATE,
+                ctx->batch.resident ? "the resident commit is a batch: read it with fri_batch_* (member-wise)" : what);
+}
+
 extern "C" int fri_layer_copy(fri_ctx* ctx, uint32_t layer, uint32_t* out, size_t cap) {
     if (!ctx || !out) return fail(ctx, FRI_EINVAL, "null argument");
     settle(ctx);
     const Plan& p = ctx->plan;
-    if (!p.valid || layer >= ctx->h_state->n_layers) return fail(ctx, FRI_ESTATE, "no such committed layer");
+    if (!p.valid || layer >= ctx->h_state->n_layers) return no_layer(ctx, "no such committed layer");
     if (layer < ctx->sharded_layers && !ctx->team_root)
         return fail(ctx, FRI_ESTATE, "layer was committed sharded: this rank holds only its block (fri_commit_sharded)");
     size_t m = (size_t)1 << (p.log_n - layer);
@@ -27,7 +34,7 @@ extern "C" int fri_tree_level_copy(fri_ctx* ctx, uint32_t layer, uint32_t level,
     if (!ctx || !out) return fail(ctx, FRI_EINVAL, "null argument");
     settle(ctx);
     const Plan& p = ctx->plan;
-    if (!p.valid || layer >= ctx->h_state->n_layers) return fail(ctx, FRI_ESTATE, "no such committed layer");
+    if (!p.valid || layer >= ctx->h_state->n_layers) return no_layer(ctx, "no such committed layer");
     if (layer < ctx->sharded_layers && !ctx->team_root)
         return fail(ctx, FRI_ESTATE, "layer was committed sharded: this rank holds only its block (fri_commit_sharded)");
     uint32_t L = p.log_n - layer;
@@ -57,7 +64,7 @@ extern "C" int fri_auth_path(fri_ctx* ctx, uint32_t layer, uint64_t index, uint3
     if (!ctx || !value_out || !depth_out) return fail(ctx, FRI_EINVAL, "null argument");
     settle(ctx);
     const Plan& p = ctx->plan;
-    if (!p.valid || layer >= ctx->h_state->n_layers) return fail(ctx, FRI_ESTATE, "no such committed layer");
+    if (!p.valid || layer >= ctx->h_state->n_layers) return no_layer(ctx, "no such committed layer");
     if (layer < ctx->sharded_layers && !ctx->team_root)
         return fail(ctx, FRI_ESTATE, "layer was committed sharded: this rank holds only its block (fri_commit_sharded)");
     uint32_t L = p.log_n - layer;
@@ -118,7 +125,7 @@ extern "C" int fri_decommit_query(fri_ctx* ctx, uint64_t index, uint32_t* values
     if (!ctx || !values || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
     settle(ctx);
     const Plan& p = ctx->plan;
-    if (!p.valid || ctx->h_state->n_layers == 0) return fail(ctx, FRI_ESTATE, "no committed layers");
+    if (!p.valid || ctx->h_state->n_layers == 0) return no_layer(ctx, "no committed layers");
     if (ctx->sharded_layers && ctx->team_root)
         return team_decommit(ctx, index, values, values_cap, paths, paths_cap, paths_len);
     if (ctx->sharded_layers)

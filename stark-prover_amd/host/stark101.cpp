@@ -286,6 +286,22 @@ std::vector<uint8_t> MerkleTree::get_authentication_path(size_t index) const {
     if (gpu_->generation() != gen_) throw Panic("FRIProof layers were replaced by a later commit on the same Gpu");
     uint32_t value = 0, depth = 0;
     std::vector<uint8_t> path(32 * 32);
+    if (member_ >= 0) {
+        // a member of a batch: the opening of `index` in layer k is at index mod 2^(log_n - k) = index
+        if (index >> (log_n_ - layer_)) throw Panic("authentication path: index out of range");
+        size_t bytes = 0, off = 0, got = 0;
+        for (uint32_t k = 0; k < n_layers_; k++) {
+            if (k == layer_) off = bytes;
+            bytes += 2 * 32 * size_t{log_n_ - k};
+        }
+        std::vector<uint32_t> values(2 * size_t{n_layers_});
+        std::vector<uint8_t> paths(bytes ? bytes : 1);
+        gpu_->check(fri_batch_decommit_query(gpu_->ctx(), static_cast<uint32_t>(member_), index, values.data(),
+                                             values.size(), paths.data(), paths.size(), &got),
+                    "fri_batch_decommit_query");
+        const size_t pb = 32 * size_t{log_n_ - layer_};
+        return std::vector<uint8_t>(paths.begin() + off, paths.begin() + off + pb);
+    }
     gpu_->check(fri_auth_path(gpu_->ctx(), layer_, index, &value, path.data(), &depth), "fri_auth_path");
     path.resize(32 * size_t{depth});
     return path;
@@ -303,7 +319,11 @@ std::vector<FE> FRIProof::fri_layer(size_t k) const {
     if (k >= n_layers()) throw Panic("no such FRI layer");
     const size_t m = size_t{1} << (log_n - k);
     std::vector<uint32_t> v(m);
-    gpu_->check(fri_layer_copy(gpu_->ctx(), static_cast<uint32_t>(k), v.data(), m), "fri_layer_copy");
+    if (member_ >= 0)
+        gpu_->check(fri_batch_layer_copy(gpu_->ctx(), static_cast<uint32_t>(member_), static_cast<uint32_t>(k), v.data(), m),
+                    "fri_batch_layer_copy");
+    else
+        gpu_->check(fri_layer_copy(gpu_->ctx(), static_cast<uint32_t>(k), v.data(), m), "fri_layer_copy");
     return to_fe(v.data(), m);
 }
 
@@ -392,6 +412,48 @@ std::vector<FRIProof> fri_commit_pipelined(const std::vector<Poly>& polys, uint3
     return out;
 }
 
+std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>& polys, uint32_t log_n, FE offset,
+                                       std::vector<FriChannel>& channels, const std::shared_ptr<Gpu>& gpu) {
+    if (channels.size() != polys.size()) throw Panic("fri_commit_batch: one channel per polynomial");
+    if (polys.empty()) return {};
+    if (!gpu) throw Panic("fri_commit: no Gpu");
+    if (gpu->n_ranks() > 1) throw Panic("fri_commit_batch: batches run on a one-device Gpu");
+    if (log_n > gpu->log_n_max()) throw Panic("fri_commit: codeword 2^" + std::to_string(log_n) + " exceeds the context");
+    const size_t B = polys.size();
+    size_t d = 0;
+    for (const Poly& p : polys) d = std::max(d, p.coefficients.size());
+    std::vector<uint32_t> coeffs(B * d, 0u);                 // ragged members: zeros up to the longest
+    std::vector<fri_channel_state> cin(B);
+    for (size_t b = 0; b < B; b++) {
+        const std::vector<uint32_t> c = to_u32(polys[b].coefficients);
+        std::copy(c.begin(), c.end(), coeffs.begin() + b * d);
+        if (!channels[b].state.empty()) {
+            auto st = sha::from_hex(channels[b].state);
+            if (st.size() != 32) throw Panic("Channel state is not a SHA-256 digest");
+            std::memcpy(cin[b].digest, st.data(), 32);
+            cin[b].has_state = 1;
+        }
+    }
+    std::vector<fri_commit_result> res(B);
+    std::vector<int> status(B, 0);
+    const uint64_t gen = gpu->bump();                        // previous layers are not served from here on
+    gpu->check(fri_commit_batch(gpu->ctx(), coeffs.data(), d, static_cast<uint32_t>(B), log_n,
+                                static_cast<uint32_t>(offset.value()), cin.data(), 0, nullptr, res.data(), status.data()),
+               "fri_commit_batch");
+    std::vector<FRIProof> out;
+    for (size_t b = 0; b < B; b++) {
+        FRIProof proof = FRIProof::mirror(res[b], log_n, gpu, channels[b], gen);
+        proof.member_ = static_cast<int>(b);
+        for (MerkleTree& t : proof.fri_merkles) {
+            t.member_ = proof.member_;
+            t.log_n_ = log_n;
+            t.n_layers_ = res[b].n_layers;
+        }
+        out.push_back(std::move(proof));
+    }
+    return out;
+}
+
 FRIProof FRIProof::mirror(const fri_commit_result& res, uint32_t log_n, const std::shared_ptr<Gpu>& gpu,
                           FriChannel& channel, uint64_t gen) {
     // The channel messages the reference's loop produced (fri_commit.rs:84-114):
@@ -449,14 +511,19 @@ namespace {
 // `layers` (optional): the caller's FRIProof.fri_layers, checked against the
 // device's openings.
 void decommit_query(const Gpu& gpu, uint32_t log_n, size_t n_layers, uint64_t index, FriChannel& channel,
-                    const std::vector<std::vector<FE>>* layers) {
+                    const std::vector<std::vector<FE>>* layers, int member = -1) {
     size_t path_bytes = 0;
     for (size_t k = 0; k < n_layers; k++) path_bytes += 2 * 32 * (log_n - k);
     std::vector<uint32_t> values(2 * n_layers);
     std::vector<uint8_t> paths(path_bytes ? path_bytes : 1);
     size_t got = 0;
-    gpu.check(fri_decommit_query(gpu.ctx(), index, values.data(), values.size(), paths.data(), paths.size(), &got),
-              "fri_decommit_query");
+    if (member >= 0)      // a member of the resident batch
+        gpu.check(fri_batch_decommit_query(gpu.ctx(), static_cast<uint32_t>(member), index, values.data(), values.size(),
+                                           paths.data(), paths.size(), &got),
+                  "fri_batch_decommit_query");
+    else
+        gpu.check(fri_decommit_query(gpu.ctx(), index, values.data(), values.size(), paths.data(), paths.size(), &got),
+                  "fri_decommit_query");
     size_t off = 0;
     for (size_t k = 0; k < n_layers; k++) {
         const size_t depth = log_n - k, pb = 32 * depth, m = size_t{1} << depth;
@@ -482,7 +549,7 @@ void decommit_query(const Gpu& gpu, uint32_t log_n, size_t n_layers, uint64_t in
 
 void decommit_fri_layers(size_t index, const FRIProof& proof, FriChannel& channel) {
     proof.require_resident();
-    decommit_query(*proof.gpu_, proof.log_n, proof.n_layers(), index, channel, nullptr);
+    decommit_query(*proof.gpu_, proof.log_n, proof.n_layers(), index, channel, nullptr, proof.member_);
 }
 
 void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel) {
@@ -500,19 +567,25 @@ void decommit_fri(size_t num_queries, size_t max_index, const std::vector<std::v
     if (!t0.gpu_) throw Panic("decommit_fri: the trees of an FRIProof are device-backed; a standalone tree keeps only its root");
     for (size_t k = 0; k < fri_merkles.size(); k++) {
         const MerkleTree& t = fri_merkles[k];
-        if (t.gpu_ != t0.gpu_ || t.gen_ != t0.gen_ || t.layer_ != k)
+        if (t.gpu_ != t0.gpu_ || t.gen_ != t0.gen_ || t.layer_ != k || t.member_ != t0.member_)
             throw Panic("decommit_fri: the trees are not the layers of one commit");
     }
     const Gpu& gpu = *t0.gpu_;
     if (gpu.generation() != t0.gen_) throw Panic("FRIProof layers were replaced by a later commit on the same Gpu");
     uint64_t g = 0;
     uint32_t log_n = 0, n_layers = 0;
-    gpu.check(fri_commit_info(gpu.ctx(), &g, &log_n, &n_layers), "fri_commit_info");
+    if (t0.member_ >= 0) {        // a member of a batch: its shape travels with its trees
+        uint32_t members = 0;
+        gpu.check(fri_batch_info(gpu.ctx(), &g, &members, &log_n), "fri_batch_info");
+        n_layers = static_cast<uint32_t>(t0.member_) < members && log_n == t0.log_n_ ? t0.n_layers_ : 0;
+    } else {
+        gpu.check(fri_commit_info(gpu.ctx(), &g, &log_n, &n_layers), "fri_commit_info");
+    }
     if (n_layers != fri_merkles.size() || fri_layers[0].size() != (size_t{1} << log_n))
         throw Panic("decommit_fri: the resident commit is not the one these trees belong to");
     for (size_t q = 0; q < num_queries; q++) {
         const uint64_t idx = channel.receive_random_int(0, max_index, true);
-        decommit_query(gpu, log_n, n_layers, idx, channel, &fri_layers);
+        decommit_query(gpu, log_n, n_layers, idx, channel, &fri_layers, t0.member_);
     }
 }
 

@@ -471,11 +471,15 @@ class MerkleTree {
     friend FRIProof fri_commit_coset(const Poly&, uint32_t, FE, FriChannel&, const std::shared_ptr<Gpu>&);
     friend std::vector<FRIProof> fri_commit_pipelined(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                       const std::shared_ptr<Gpu>&);
+    friend std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
+                                                  const std::shared_ptr<Gpu>&);
     MerkleTree() = default;
     std::string root_hex_;
     std::shared_ptr<Gpu> gpu_;
     uint64_t gen_ = 0;
     uint32_t layer_ = 0;
+    int member_ = -1;        // >= 0: a tree of that member of a batch (fri_commit_batch)
+    uint32_t log_n_ = 0, n_layers_ = 0;   // (a member's tree: its commit's shape)
 };
 
 // fri_commit.rs:9-13.  fri_layers are read back from HBM on demand.
@@ -487,6 +491,8 @@ class FRIProof {
     uint32_t log_n = 0;
 
     size_t n_layers() const { return fri_merkles.size(); }
+    // >= 0: the proof's member of the batch that made it (fri_commit_batch)
+    int member() const { return member_; }
     std::vector<FE> fri_layer(size_t k) const;
     std::vector<std::vector<FE>> fri_layers() const;
     // true while the Gpu has not committed anything since (layers resident)
@@ -496,6 +502,8 @@ class FRIProof {
     friend FRIProof fri_commit_coset(const Poly&, uint32_t, FE, FriChannel&, const std::shared_ptr<Gpu>&);
     friend std::vector<FRIProof> fri_commit_pipelined(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                       const std::shared_ptr<Gpu>&);
+    friend std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
+                                                  const std::shared_ptr<Gpu>&);
     friend void decommit_fri_layers(size_t, const FRIProof&, FriChannel&);
     friend StarkProof prove_fibsq(FE, uint32_t, uint32_t, size_t, FriChannel&, FE, std::shared_ptr<Gpu>);
     // The proof of a device commit: appends the messages the device sent
@@ -506,6 +514,7 @@ class FRIProof {
                            FriChannel& channel, uint64_t gen = 0);
     std::shared_ptr<Gpu> gpu_;
     uint64_t gen_ = 0;
+    int member_ = -1;
     void require_resident() const;
 };
 
@@ -527,6 +536,15 @@ FRIProof fri_commit_coset(const Poly& poly, uint32_t log_n, FE offset, FriChanne
 // and trees stay resident (the earlier ones report resident() == false).
 std::vector<FRIProof> fri_commit_pipelined(const std::vector<Poly>& polys, uint32_t log_n, FE offset,
                                            std::vector<FriChannel>& channels, const std::shared_ptr<Gpu>& gpu);
+
+// fri_commit (fri_commit.rs:72-122) of many small polynomials, each with its
+// own channel, in ONE device call (fri_commit_batch: one workgroup per member,
+// log_n <= FRI_BATCH_MAX_LOG_N, a one-device Gpu).  Proof i equals
+// fri_commit_coset(polys[i], ..., channels[i]) and remembers its member:
+// every proof's layers, trees and decommitments are served until the next
+// commit on the Gpu.  Members of different lengths are padded with zeros.
+std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>& polys, uint32_t log_n, FE offset,
+                                       std::vector<FriChannel>& channels, const std::shared_ptr<Gpu>& gpu);
 
 // fri_commit.rs:137-179 over the device-resident layers and trees.
 void decommit_fri_layers(size_t index, const FRIProof& proof, FriChannel& channel);

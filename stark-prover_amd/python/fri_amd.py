@@ -43,6 +43,9 @@ FLAG_NO_GRAPH = 2
 FLAG_RANK_INPUTS = 4      # FRI_FLAG_RANK_INPUTS (fri_amd.h): team commit from the ranks' resident inputs
 MAX_INFLIGHT = 4          # FRI_MAX_INFLIGHT (fri_amd.h): pipelined commits pending per context
 DEFAULT_LANES = 3         # FRI_DEFAULT_LANES (fri_amd.h): commit lanes of a context
+BATCH_MAX_LOG_N = 18      # FRI_BATCH_MAX_LOG_N (fri_amd.h): largest codeword of fri_commit_batch
+BATCH_LDE_LDS_MAX_LOG_N = 12   # FRI_BATCH_LDE_LDS_MAX_LOG_N: the batch's LDE runs in LDS up to here
+BATCH_MAX = 65535         # members of one fri_commit_batch call
 POLY_FORCE_NTT = 1        # FRI_POLY_FORCE_* (fri_amd.h): fri_poly_mul's test/measurement hooks
 POLY_FORCE_DIRECT = 2
 POLY_DIRECT_LIMIT = 4096  # FRI_POLY_DIRECT_LIMIT: the direct kernel's hard limit (short operand)
@@ -182,6 +185,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_ctx_set_lanes": (i32, [vp, u32]),
         "fri_debug_ticket_lane": (i32, [vp, ctypes.c_uint64, ctypes.POINTER(i32)]),
         "fri_commit_degrees": (i32, [vp, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(u32)]),
+        "fri_commit_batch": (i32, [vp, pu32, sz, u32, u32, u32, ctypes.POINTER(ChannelState), u32, pu32,
+                                   ctypes.POINTER(CommitResult), ctypes.POINTER(i32)]),
+        "fri_commit_batch_device": (i32, [vp, vp, sz, u32, u32, u32, ctypes.POINTER(ChannelState), u32, pu32,
+                                          ctypes.POINTER(CommitResult), ctypes.POINTER(i32)]),
+        "fri_batch_info": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "fri_batch_layer_copy": (i32, [vp, u32, u32, pu32, sz]),
+        "fri_batch_tree_level_copy": (i32, [vp, u32, u32, u32, ctypes.c_char_p, sz]),
+        "fri_batch_commit_degrees": (i32, [vp, u32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(u32)]),
+        "fri_batch_decommit_query": (i32, [vp, u32, ctypes.c_uint64, pu32, sz, ctypes.c_char_p, sz,
+                                           ctypes.POINTER(sz)]),
         "fri_debug_transport_log": (i32, [vp, ctypes.POINTER(TransportOp), sz, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
@@ -502,6 +515,92 @@ class Context:
         res = out if out is not None else CommitResult()
         self._check(self.lib.fri_commit_wait(self.h, ticket, ctypes.byref(res)))
         return res
+
+    # ---- batched commit ----------------------------------------------------
+    def commit_batch(self, polys, log_n: int, offset: int = GENERATOR, channel_states=None, forced_betas=None,
+                     d_coeffs: Optional[int] = None, d: Optional[int] = None, batch: Optional[int] = None):
+        """fri_commit_batch: one CommitResult per member of ``polys`` (ragged
+        members are padded with zeros to the longest).  channel_states: per
+        member 32 digest bytes or None (fresh); forced_betas: per member a
+        sequence of betas (test hook).  With ``d_coeffs`` (a device pointer to
+        batch*d words) instead of polys: fri_commit_batch_device.  A member
+        that failed raises FriError after the call; ``self.batch_status``
+        keeps every member's code."""
+        if d_coeffs is None:
+            c, d = _pack_batch(polys)
+            batch = c.shape[0]
+            if batch == 0:
+                self.batch_status = []
+                return []
+        chs = None
+        if channel_states is not None:
+            if len(channel_states) != batch:
+                raise FriError(FRI_EINVAL, "one channel state per member")
+            chs = (ChannelState * batch)()
+            for b, st in enumerate(channel_states):
+                if st:
+                    ctypes.memmove(chs[b].digest, st, 32)
+                    chs[b].has_state = 1
+        flags, fb = 0, None
+        if forced_betas is not None:
+            if len(forced_betas) != batch:
+                raise FriError(FRI_EINVAL, "one sequence of forced betas per member")
+            fb = np.zeros((batch, MAX_ROUNDS), dtype=np.uint32)
+            for b, row in enumerate(forced_betas):
+                fb[b, : len(row)] = row
+            flags |= FLAG_FORCE_BETAS
+        res = (CommitResult * batch)()
+        status = (ctypes.c_int * batch)()
+        fbp = _ptr(fb) if fb is not None else None
+        if d_coeffs is None:
+            rc = self.lib.fri_commit_batch(self.h, _ptr(c), d, batch, log_n, offset, chs, flags, fbp, res, status)
+        else:
+            rc = self.lib.fri_commit_batch_device(self.h, d_coeffs, d, batch, log_n, offset, chs, flags, fbp, res,
+                                                  status)
+        self.batch_status = [int(x) for x in status]     # (all zero after a refused call: it writes nothing)
+        self.batch_results = list(res)
+        self._check(rc)
+        return list(res)
+
+    def batch_info(self):
+        """(generation, members, log_n) of the resident batch; members = 0 when
+        the last commit on the context was not a batch (fri_batch_info)."""
+        g, b, ln = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self.lib.fri_batch_info(self.h, ctypes.byref(g), ctypes.byref(b), ctypes.byref(ln)))
+        return g.value, b.value, ln.value
+
+    def batch_layer(self, member: int, k: int, log_n: int) -> np.ndarray:
+        out = np.empty(1 << (log_n - k), dtype=np.uint32)
+        self._check(self.lib.fri_batch_layer_copy(self.h, member, k, _ptr(out), out.size))
+        return out
+
+    def batch_tree_level(self, member: int, k: int, level: int, log_n: int) -> List[bytes]:
+        cnt = 1 << (log_n - k - level)
+        buf = ctypes.create_string_buffer(32 * cnt)
+        self._check(self.lib.fri_batch_tree_level_copy(self.h, member, k, level, buf, 32 * cnt))
+        raw = buf.raw
+        return [raw[32 * i: 32 * i + 32] for i in range(cnt)]
+
+    def batch_commit_degrees(self, member: int) -> List[int]:
+        out = (ctypes.c_int32 * (MAX_ROUNDS + 1))()
+        n = ctypes.c_uint32()
+        self._check(self.lib.fri_batch_commit_degrees(self.h, member, out, MAX_ROUNDS + 1, ctypes.byref(n)))
+        return [int(out[k]) for k in range(n.value)]
+
+    def batch_decommit_query(self, member: int, index: int, n_layers: int, log_n: int):
+        """fri_batch_decommit_query: decommit_query's tuples for one member."""
+        vals = np.empty(2 * n_layers, dtype=np.uint32)
+        total = sum(64 * (log_n - k) for k in range(n_layers))
+        buf = ctypes.create_string_buffer(max(total, 1))
+        ln = ctypes.c_size_t()
+        self._check(self.lib.fri_batch_decommit_query(self.h, member, index, _ptr(vals), vals.size, buf, total,
+                                                      ctypes.byref(ln)))
+        out, off = [], 0
+        for k in range(n_layers):
+            pl = 32 * (log_n - k)
+            out.append((int(vals[2 * k]), int(vals[2 * k + 1]), buf.raw[off:off + pl], buf.raw[off + pl:off + 2 * pl]))
+            off += 2 * pl
+        return out
 
     def commit_info(self):
         """(generation, log_n, n_layers) of the resident commit (fri_commit_info)."""
@@ -911,10 +1010,57 @@ class MerkleTree:
         return b"".join(path)
 
 
+class BatchMember:
+    """One member of a context's resident batch (fri_commit_batch) behind the
+    read-back interface of a Context: what FRIProof, MerkleTree and the
+    decommitment functions call (layer, tree_level, auth_path, decommit_query,
+    commit_info, commit_degrees), served by the fri_batch_* read-backs."""
+
+    def __init__(self, ctx: Context, member: int):
+        self.ctx, self.member = ctx, member
+
+    def commit_info(self):
+        g, b, ln = self.ctx.batch_info()
+        return g, (ln if b else 0), (len(self.commit_degrees()) if b else 0)
+
+    def _resident(self, log_n: int, generation: Optional[int] = None) -> None:
+        g, b, ln = self.ctx.batch_info()
+        if generation is not None and g != generation:
+            raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
+        if b and ln != log_n:
+            raise FriError(FRI_ESTATE, f"resident batch is 2^{ln}, not 2^{log_n}")
+
+    def commit_degrees(self) -> List[int]:
+        return self.ctx.batch_commit_degrees(self.member)
+
+    def layer(self, k: int, log_n: int, generation: Optional[int] = None) -> np.ndarray:
+        self._resident(log_n, generation)
+        return self.ctx.batch_layer(self.member, k, log_n)
+
+    def tree_level(self, k: int, level: int, log_n: int) -> List[bytes]:
+        self._resident(log_n)
+        return self.ctx.batch_tree_level(self.member, k, level, log_n)
+
+    def decommit_query(self, index: int, n_layers: int, log_n: int, generation: Optional[int] = None,
+                       sharded: bool = False):
+        self._resident(log_n, generation)
+        if n_layers != len(self.commit_degrees()):
+            raise FriError(FRI_ESTATE, "layer count differs from the resident member's")
+        return self.ctx.batch_decommit_query(self.member, index, n_layers, log_n)
+
+    def auth_path(self, k: int, index: int, log_n: int):
+        # the opening of `index` in layer k is at idx_k = index mod 2^(log_n - k) = index
+        self._resident(log_n)
+        if not 0 <= index < (1 << (log_n - k)):
+            raise FriError(FRI_EINVAL, "index out of range")
+        val, _, path, _ = self.ctx.batch_decommit_query(self.member, index, len(self.commit_degrees()), log_n)[k]
+        return val, [path[32 * i: 32 * i + 32] for i in range(log_n - k)]
+
+
 @dataclass
 class FRIProof:
     """src/fri/fri_commit.rs:9-13 — layers/merkles read back lazily from the device."""
-    ctx: Context
+    ctx: Context             # (a BatchMember for a proof made by fri_commit_batch)
     log_n: int
     roots: List[bytes]
     betas: List[int]
@@ -922,6 +1068,7 @@ class FRIProof:
     final_degree: int
     generation: int = 0      # fri_commit_info generation of the commit that made it
     sharded: bool = False    # made by fri_commit_sharded: decommitments are collective
+    member: Optional[int] = None   # made by fri_commit_batch: its member of that batch
 
     @property
     def n_layers(self) -> int:
@@ -1374,6 +1521,51 @@ def fri_commit_pipelined(polys: Sequence[Sequence[int]], log_n: int, channels: S
                 ctxs[j].commit_wait(t)
             except FriError:
                 pass
+    return out
+
+
+_BATCH_CTX = {}     # fri_commit_batch's one-device contexts beside a default team, by size bound
+
+
+def _pack_batch(polys) -> tuple:
+    """The members' coefficients as one (batch, d) uint32 array, d the longest
+    member's length, shorter members padded with zeros (trailing zero
+    coefficients do not change a commit).  Returns (array, d)."""
+    rows = [_u32(p).reshape(-1) for p in polys]
+    d = max((r.size for r in rows), default=0)
+    c = np.zeros((len(rows), d), dtype=np.uint32)
+    for b, r in enumerate(rows):
+        c[b, : r.size] = r
+    return c, d
+
+
+def fri_commit_batch(polys: Sequence[Sequence[int]], log_n: int, channels: Sequence[Channel],
+                     offset: int = GENERATOR, ctx: Optional[Context] = None) -> List[FRIProof]:
+    """fri_commit (fri_commit.rs:72-122) of many small polynomials, each with
+    its own channel, in ONE device call (fri_commit_batch: one workgroup per
+    member; log_n <= BATCH_MAX_LOG_N).  Proof i equals fri_commit of polys[i]
+    into channels[i] and remembers its member: its layers, trees and
+    decommitments are served until the next commit on the context.  Members
+    of different lengths are padded with zeros to the longest."""
+    if len(polys) != len(channels):
+        raise FriError(FRI_EINVAL, "one channel per polynomial")
+    if len(polys) == 0:
+        return []
+    ctx = ctx or _default_ctx(log_n)
+    if ctx.n_ranks > 1:
+        # batches run on one device: a context of their own beside the default team
+        key = max(log_n, 12)
+        if key not in _BATCH_CTX:
+            _BATCH_CTX[key] = Context(0, key)
+        ctx = _BATCH_CTX[key]
+    states = [bytes.fromhex(ch.state) if ch.state else None for ch in channels]
+    res = ctx.commit_batch(polys, log_n, offset, channel_states=states)
+    gen = ctx.batch_info()[0]
+    out = []
+    for b, (r, ch) in enumerate(zip(res, channels)):
+        proof = _mirror_commit(r, BatchMember(ctx, b), log_n, ch, generation=gen)
+        proof.member = b
+        out.append(proof)
     return out
 
 
