@@ -562,9 +562,12 @@ int fri_decommit_query(fri_ctx* ctx, uint64_t index, uint32_t* values, size_t va
  * 1-8 GPUs from one host thread").  devices: the HIP
  * ordinals of ranks 0..n-1 (NULL: 0..n-1); an ordinal may repeat (several
  * ranks on one GPU; peer transport only).  n_devices: a power of two <= 64;
- * 1 gives an ordinary context.  log_n_max: the largest codeword; every
- * rank's context is shard-sized (2^(log_n_max - log2 n), and at least
- * 2^min(log_n_max, 19) for the commits rank 0 runs alone).  transport:
+ * 1 gives an ordinary context.  log_n_max: the largest codeword, and the
+ * bound of every other call on the context.  The contexts of ranks 1..n-1
+ * are shard-sized (2^(log_n_max - log2 n), and at least 2^min(log_n_max,
+ * 19)); rank 0's, which also runs the commits below the sharding threshold
+ * and the kernel-level calls alone, holds twiddles and scratch for
+ * 2^log_n_max (20 bytes per element on devices[0]).  transport:
  *   FRI_TRANSPORT_PEER  device copies between the ranks' buffers: one pull
  *                       kernel per collective reading the other ranks'
  *                       memory over xGMI peer access (hipMemcpyPeerAsync per
@@ -589,7 +592,12 @@ int fri_decommit_query(fri_ctx* ctx, uint64_t index, uint32_t* values, size_t va
  *     (and _sharded) serve every layer: the sharded ones are assembled from
  *     the ranks' blocks and the replicated top trees;
  *   fri_ctx_device_bytes: the sum over the ranks;
- *   the kernel-level calls (fri_lde, fri_merkle_root, ...) run on rank 0;
+ *   the kernel-level calls (fri_lde, fri_interpolate, fri_fold,
+ *     fri_merkle_root, fri_batch_inverse, fri_evaluate*,
+ *     fri_interpolate_points*, fri_poly_*, fri_poly_from_roots,
+ *     fri_lagrange_basis, fri_trace_commit, fri_fibsq_composition_commit)
+ *     run on rank 0 alone, up to the sizes a one-device context of
+ *     log_n_max takes, and leave a resident sharded commit readable;
  *   fri_commit_*async and fri_dist_attach_* / fri_dist_detach: FRI_EINVAL.
  * Not re-entrant (one host thread at a time), like every context.
  * fri_ctx_destroy(ctx) releases every rank. */

@@ -194,7 +194,11 @@ extern "C" int fri_ctx_create_multi(const int* devices, uint32_t n, uint32_t log
     if (n == 1) return fri_ctx_create(dev[0], log_n_max, out);
     uint32_t logG = 0;
     while ((1u << logG) < n) logG++;
-    // rank contexts are shard-sized; rank 0 also commits < 2^20 codewords alone
+    // ranks 1..G-1 are shard-sized.  Rank 0 also commits < 2^20 codewords alone
+    // and serves the kernel-level calls (fri_lde, fri_merkle_root, ...), whose
+    // bound is the caller's log_n_max: it is created with that.  No kernel
+    // reads a context's bound (the twiddles are stage-packed, the scratch only
+    // has to be large enough), so ranks of different capacity commit together.
     const uint32_t sub = std::max(log_n_max > logG ? log_n_max - logG : 1u, std::min(log_n_max, SHARD_MIN_LOG - 1));
     Team* T = new Team();
     T->G = n;
@@ -224,7 +228,7 @@ extern "C" int fri_ctx_create_multi(const int* devices, uint32_t n, uint32_t log
         return code;
     };
     for (uint32_t r = 0; r < n; r++)
-        if ((rc = fri_ctx_create(dev[r], sub, &T->rk[r]))) return undo(rc);
+        if ((rc = fri_ctx_create(dev[r], r ? sub : log_n_max, &T->rk[r]))) return undo(rc);
     for (uint32_t r = 0; r < n; r++) {
         if (hipSetDevice(dev[r]) != hipSuccess ||
             hipEventCreateWithFlags(&T->ev_ready[r], hipEventDisableTiming) != hipSuccess ||

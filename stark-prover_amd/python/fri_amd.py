@@ -275,7 +275,8 @@ class Context:
         if rc != FRI_OK:
             raise FriError(rc, f"fri_ctx_create_default({log_n_max}) failed (FRI_DEVICES="
                                f"{os.environ.get('FRI_DEVICES', '')!r}; no gfx950 device?)")
-        c = cls(0, log_n_max, _handle=h)
+        first = os.environ.get("FRI_DEVICES", "").split(",")[0].strip()      # rank 0's device (validated by the call)
+        c = cls(int(first) if first else 0, log_n_max, _handle=h)
         c.n_ranks = n.value
         return c
 
@@ -1486,12 +1487,15 @@ def fri_commit_pipelined(polys: Sequence[Sequence[int]], log_n: int, channels: S
     ``ctx`` is one Context or a list of them: with several, the commits are
     dealt round-robin and run concurrently, one stream each.
     Proof i equals fri_commit of polys[i] into channels[i]; on each context
-    only its last proof's layers stay resident."""
+    only its last proof's layers stay resident.  Without ``ctx`` the commits
+    run on the default context; where that is a team (which takes no
+    pipelined commits, fri_commit_async), on a one-device context of their
+    own on the team's first device, kept per size bound."""
     if len(polys) != len(channels):
         raise FriError(FRI_EINVAL, "one channel per polynomial")
     if not 1 <= depth <= MAX_INFLIGHT:
         raise FriError(FRI_EINVAL, "depth must be 1..MAX_INFLIGHT")
-    ctxs = list(ctx) if isinstance(ctx, (list, tuple)) else [ctx or _default_ctx(log_n)]
+    ctxs = list(ctx) if isinstance(ctx, (list, tuple)) else [ctx or _beside_team(_default_ctx(log_n), log_n, _PIPE_CTX)]
     if len({id(c) for c in ctxs}) != len(ctxs):
         raise FriError(FRI_EINVAL, "a context appears twice: pass each context once (depth sets the commits in flight)")
     gen = [c.commit_info()[0] for c in ctxs]     # every enqueued commit bumps its context's generation by one
@@ -1525,6 +1529,19 @@ def fri_commit_pipelined(polys: Sequence[Sequence[int]], log_n: int, channels: S
 
 
 _BATCH_CTX = {}     # fri_commit_batch's one-device contexts beside a default team, by size bound
+_PIPE_CTX = {}      # fri_commit_pipelined's
+
+
+def _beside_team(ctx: Context, log_n: int, cache: dict) -> Context:
+    """``ctx`` itself unless it is a team: then the one-device context of
+    ``cache`` for 2^log_n (2^12 minimum) on the team's first device, created
+    on first use and kept."""
+    if ctx.n_ranks == 1:
+        return ctx
+    key = max(log_n, 12)
+    if key not in cache:
+        cache[key] = Context(ctx.device, key)
+    return cache[key]
 
 
 def _pack_batch(polys) -> tuple:
@@ -1551,13 +1568,8 @@ def fri_commit_batch(polys: Sequence[Sequence[int]], log_n: int, channels: Seque
         raise FriError(FRI_EINVAL, "one channel per polynomial")
     if len(polys) == 0:
         return []
-    ctx = ctx or _default_ctx(log_n)
-    if ctx.n_ranks > 1:
-        # batches run on one device: a context of their own beside the default team
-        key = max(log_n, 12)
-        if key not in _BATCH_CTX:
-            _BATCH_CTX[key] = Context(0, key)
-        ctx = _BATCH_CTX[key]
+    # batches run on one device: a context of their own beside a (default) team
+    ctx = _beside_team(ctx or _default_ctx(log_n), log_n, _BATCH_CTX)
     states = [bytes.fromhex(ch.state) if ch.state else None for ch in channels]
     res = ctx.commit_batch(polys, log_n, offset, channel_states=states)
     gen = ctx.batch_info()[0]

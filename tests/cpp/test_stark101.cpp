@@ -7,6 +7,7 @@
 //   gpu: fri_commit / decommit_fri / MerkleTree / interpolate / batch
 //        inverse through libfri_amd.so against tests/golden (bit-exact).
 // Usage: test_stark101 [cpu|gpu|all]; exit status = number of failures.
+//        test_stark101 refsig LOG_N OUT | defteam OUT_DIR (below).
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -638,9 +639,79 @@ static int refsig(uint32_t log_n, const char* out_path) {
     return fails;
 }
 
+// ---------------------------------------------------------------------------
+// `test_stark101 defteam OUT_DIR`: the calls of the mirror that name no Gpu,
+// at the first size a shard-sized rank 0 of a default team would refuse
+// (2^20), on the default devices (FRI_DEVICES; tests/test_cpp_host.py runs it
+// with "0,0", a two-rank team on one GPU): MerkleTree, evaluate_on_coset,
+// interpolate, batch_inverse, prove_fibsq and a Polynomial product.  Inputs
+// are splitmix64 streams (seeds below); every result goes to OUT_DIR for the
+// test to compare with the C oracle: arrays as raw little-endian uint32
+// (NAME.u32), the rank count, the Merkle root and the proof's state and
+// messages as lines of defteam.txt (as refsig writes them).
+static std::vector<FE> seeded_fe(uint64_t seed, size_t n) {
+    std::vector<FE> v(n);
+    for (size_t i = 0; i < n; i++) v[i] = FE(splitmix64_at(seed, i) % P);
+    return v;
+}
+static bool write_u32(const std::string& dir, const char* name, const std::vector<FE>& v) {
+    std::vector<uint32_t> w(v.size());
+    for (size_t i = 0; i < v.size(); i++) w[i] = static_cast<uint32_t>(v[i].value());
+    FILE* f = std::fopen((dir + "/" + name + ".u32").c_str(), "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(w.data(), 4, w.size(), f) == w.size();
+    return std::fclose(f) == 0 && ok;
+}
+static int defteam(const std::string& dir) {
+    const uint32_t L = 20;
+    const size_t n = size_t{1} << L;
+    bool ok = true;
+    // MerkleTree over 2^20 elements
+    const std::string root = MerkleTree(seeded_fe(51, n)).root();
+    // evaluate_on_coset at 2^20, and interpolate of its output on the same coset
+    const Coset co(FE(FRI_GENERATOR), omega(L), n);
+    const std::vector<FE> lde = evaluate_on_coset(Poly(seeded_fe(52, n >> 3)), co);
+    ok = write_u32(dir, "lde", lde) && ok;
+    ok = write_u32(dir, "interp", interpolate(co.generate_coset_domain(), lde).coefficients) && ok;
+    // batch_inverse of 2^20 values, zeros at both ends and in the middle
+    std::vector<FE> xs = seeded_fe(53, n);
+    xs[0] = xs[n / 2] = xs[n - 1] = FE(0);
+    ok = write_u32(dir, "inv", batch_inverse(xs)) && ok;
+    // prove_fibsq at log_t = 17, blowup 8, 2 queries
+    FriChannel ch;
+    StarkProof sp = prove_fibsq(FE(3141592), 17, 3, 2, ch);
+    // a Polynomial product that needs a 2^20 transform
+    const Poly prod = Poly(seeded_fe(54, (n >> 2) + 1)) * Poly(seeded_fe(55, (n >> 2) + 1));
+    ok = write_u32(dir, "prod", prod.coefficients) && ok;
+    FILE* f = std::fopen((dir + "/defteam.txt").c_str(), "w");
+    if (!f) return 2;
+    std::fprintf(f, "ranks %u\n", Gpu::thread_default(L)->n_ranks());
+    std::fprintf(f, "merkle %s\n", root.c_str());
+    std::fprintf(f, "layers %zu\n", sp.fri.n_layers());
+    std::fprintf(f, "state %s\n", ch.state.c_str());
+    for (const auto& m : ch.proof) std::fprintf(f, "msg %s\n", sha::hex(m.data(), m.size()).c_str());
+    std::fclose(f);
+    int fails = ok ? 0 : 1;
+    if (!verify_fibsq(ch.proof, sp.a_last, 17, 3, 2, sp.fri.n_layers())) {
+        std::printf("FAIL defteam: verify_fibsq rejects the proof\n");
+        fails++;
+    }
+    std::printf("defteam 2^%u: %zu messages, %d failures\n", L, ch.proof.size(), fails);
+    return fails;
+}
+
 int main(int argc, char** argv) {
     const std::string which = argc > 1 ? argv[1] : "cpu";
     if (which == "refsig") return argc > 3 ? refsig(static_cast<uint32_t>(std::atoi(argv[2])), argv[3]) : 2;
+    if (which == "defteam") {
+        if (argc <= 2) return 2;
+        try {
+            return defteam(argv[2]);
+        } catch (const std::exception& e) {
+            std::printf("FAIL defteam: exception: %s\n", e.what());
+            return 1;
+        }
+    }
     int fails = 0, ran = 0;
     for (auto& t : registry()) {
         if (which != "all" && which != t.group) continue;

@@ -104,3 +104,56 @@ def test_cpp_reference_signatures_on_default_team(tmp_path, corc):
     assert len(msgs) == len(want_msgs)
     assert msgs == want_msgs
     assert state == want_state
+
+
+@pytest.mark.gpu
+def test_cpp_no_context_calls_on_default_team(tmp_path, corc, oracle):
+    """The C++ mirror's calls that name no Gpu, on a default team of two ranks
+    (FRI_DEVICES "0,0"), at 2^20: the first size a shard-sized rank 0 would
+    refuse.  MerkleTree, evaluate_on_coset, interpolate, batch_inverse,
+    prove_fibsq (log_t = 17, blowup 8, 2 queries) and a Polynomial product of
+    two operands of 2^18 + 1 coefficients; every result the binary writes
+    (tests/cpp/test_stark101.cpp defteam) is compared with the C oracle."""
+    import numpy as np
+
+    import fri_oracle as fo
+    from prover_check import oracle_fibsq_proof
+    from test_gpu_tier_sweep import P, _p, c_interpolate_coset, c_lde, c_merkle_nodes, horner_all, same
+    _build()
+    env = dict(os.environ, FRI_DEVICES="0,0")
+    p = subprocess.run([BIN, "defteam", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    lines = (tmp_path / "defteam.txt").read_text().split("\n")
+    assert lines[0] == "ranks 2", lines[0]
+    L = 20
+    n = 1 << L
+
+    def read(name):
+        return np.fromfile(tmp_path / (name + ".u32"), dtype="<u4")
+
+    assert lines[1] == "merkle " + c_merkle_nodes(corc, fo.splitmix64_np(51, n))[-32:].tobytes().hex()
+    coeffs = fo.splitmix64_np(52, n >> 3)
+    want_lde = c_lde(corc, coeffs, L, 5)
+    same(read("lde"), want_lde, "evaluate_on_coset at 2^20")
+    same(read("interp"), c_interpolate_coset(corc, want_lde, L, 5), "interpolate at 2^20")
+    xs = fo.splitmix64_np(53, n).copy()
+    xs[0] = xs[n // 2] = xs[n - 1] = 0
+    want_inv = np.empty(n, dtype=np.uint64)
+    corc.orc_batch_inverse(_p(xs), _p(want_inv), n, P)
+    same(read("inv"), want_inv, "batch_inverse of 2^20 values")
+    res, _, _, _, want_msgs, want_state = oracle_fibsq_proof(corc, oracle, 3141592, 17, 3, 2)
+    assert lines[2] == f"layers {res.n_layers}"
+    assert lines[3].split()[1] == want_state
+    msgs = [bytes.fromhex(ln.split()[1]) if len(ln.split()) > 1 else b"" for ln in lines[4:] if ln.startswith("msg")]
+    assert len(msgs) == len(want_msgs)
+    assert msgs == want_msgs
+    # the product: its exact ends, and (ab)(x) = a(x) b(x) at 8 seeded points
+    la = (n >> 2) + 1
+    a, b = fo.splitmix64_np(54, la), fo.splitmix64_np(55, la)
+    assert a[-1] and b[-1]
+    prod = read("prod")
+    assert prod.size == 2 * la - 1
+    assert int(prod[0]) == int(a[0]) * int(b[0]) % P and int(prod[-1]) == int(a[-1]) * int(b[-1]) % P
+    pts = fo.splitmix64_np(56, 8)
+    got, fa, fb = horner_all(corc, prod, pts), horner_all(corc, a, pts), horner_all(corc, b, pts)
+    assert [int(v) for v in got] == [int(x) * int(y) % P for x, y in zip(fa, fb)]

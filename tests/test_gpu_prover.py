@@ -21,17 +21,6 @@ def _proof_sha(msgs):
     return hashlib.sha256(b"".join(len(m).to_bytes(4, "little") + m for m in msgs)).hexdigest()
 
 
-def _levels(nodes: bytes, m: int):
-    """orc_merkle_build layout (leaves first, power-of-two m) -> list of levels."""
-    out, off = [], 0
-    while True:
-        out.append([nodes[32 * (off + i): 32 * (off + i + 1)] for i in range(m)])
-        off += m
-        if m == 1:
-            return out
-        m //= 2
-
-
 def test_prove_matches_golden_transcripts(ctx, golden):
     import fri_amd
     for c in golden["fibsq"]:
@@ -51,53 +40,11 @@ def test_prove_matches_c_oracle(ctx, corc, oracle, log_t, lb, queries):
     the smallest cosets the entry point accepts: 8 points (fewer than one
     composition lane's 16) and 16."""
     import fri_amd
+    from prover_check import check_proof_matches_c_oracle
     a1 = 3141592
-    L = log_t + lb
-    n, B = 1 << L, 1 << lb
     ch = fri_amd.Channel()
     pr = fri_amd.prove_fibsq(a1, log_t, lb, queries, ch, ctx=ctx)
-    # oracle: commit phase in C, keeping trace LDE / trace tree / FRI layers / trees
-    och = oracle.OrcChannel()
-    corc.orc_channel_init(ctypes.byref(och))
-    root = ctypes.create_string_buffer(32)
-    al = (ctypes.c_uint64 * 3)()
-    res = oracle.OrcFriResult()
-    fe = np.zeros(n, dtype=np.uint64)
-    ftree = ctypes.create_string_buffer(32 * (2 * n - 1))
-    lay = np.zeros(2 * n, dtype=np.uint64)
-    tsz = sum(2 * (n >> k) - 1 for k in range(L + 1))
-    trees = ctypes.create_string_buffer(32 * tsz)
-    pu = ctypes.POINTER(ctypes.c_uint64)
-    assert corc.orc_fibsq_prove_commit(a1, log_t, lb, 5, 5, P, ctypes.byref(och), root, al, ctypes.byref(res),
-                                       fe.ctypes.data_as(pu), ftree, lay.ctypes.data_as(pu), trees) == 0
-    assert pr.trace_root == root.raw and pr.alphas == list(al)
-    assert pr.fri.roots == [bytes(res.roots[k]) for k in range(res.n_layers)]
-    assert pr.fri.betas == [int(res.betas[k]) for k in range(res.n_rounds)]
-    assert pr.fri.final_value == res.final_value and pr.fri.final_degree == res.final_degree
-    # deg CP = T: the folds end at a constant after log_t + 1 rounds.  T = 4 is
-    # the exception: g^2 = -1 there, so the leading terms of f(g x)^2 and f(x)^2
-    # cancel (1 + g^(2(T-1)) = 0), deg CP = 3 and two rounds reach the constant
-    assert res.n_rounds == (log_t + 1 if log_t > 2 else 2)
-    # decommitment over the oracle's data, channel continued from the oracle state
-    flev = _levels(ftree.raw, n)
-    layers, tlev, lo, to = [], [], 0, 0
-    for k in range(res.n_layers):
-        m = n >> k
-        layers.append([int(v) for v in lay[lo:lo + m]])
-        tlev.append(_levels(trees.raw[32 * to: 32 * (to + 2 * m - 1)], m))
-        lo += m
-        to += 2 * m - 1
-    ref = oracle.Channel(state=och.state.decode())
-    for _ in range(queries):
-        idx = ref.receive_random_int(0, n - 2 * B - 1, True)
-        for j in range(3):
-            ref.send(oracle.fe_to_bytes(int(fe[idx + j * B])))
-            ref.send(oracle.merkle_proof(flev, idx + j * B))
-        oracle.decommit_fri_layers(idx, layers, tlev, ref)
-    assert ch.state == ref.state
-    assert ch.proof[-len(ref.proof):] == ref.proof
-    assert fri_amd.verify_fibsq(ch.proof, fri_amd.fibsq_trace(a1, 1 << log_t)[-1], log_t, lb, queries,
-                                len(pr.fri.roots))
+    check_proof_matches_c_oracle(fri_amd, corc, oracle, pr, ch, a1, log_t, lb, queries)
 
 
 def test_prove_verify_rejects_tampering(ctx):

@@ -368,6 +368,11 @@ def test_team_2p28_world8_configs4(oracle_commit, copy):
         res = cx.commit(cf, L)
         want = oracle_commit(L, 42)
         assert _transcript(res) == want
+        # rank 0 also holds the twiddles and scratch of the caller's log_n_max (README)
+        per_rank = [cx.team_rank(r).device_bytes()[0] for r in range(1, 8)]
+        per_rank.insert(0, cx.device_bytes()[0] - sum(per_rank))       # (the team's context reports the sum)
+        for r in (0, 1):
+            print(f"team 2^{L} x 8, rank {r}: {per_rank[r]} bytes of HBM ({per_rank[r] / 2 ** 30:.2f} GiB)")
         q = cx.decommit_query(123456789, res.n_layers, L)
         for k, (v, sv, path, spath) in enumerate(q):
             m = 1 << (L - k)
