@@ -465,8 +465,26 @@ inline void forward(fri_ctx* ctx, const uint32_t* src, size_t len, uint32_t log_
     NttPlan p = lde_plan(ctx, log_N);
     launch_ntt(p, src, len, dst, ctx->stream);
 }
+// Every 2^lg block of an np-word level (np >= 2^lg) in batched launches: block
+// j transforms src[j * 2^lg .. + len), zero beyond len, into dst[j * 2^lg ..).
+// A launch carries at most 2^15 transforms, so there is more than one chunk
+// only beyond 2^28 words.  A level that transforms several operands calls
+// this once per operand: with more than one chunk the launches then reach the
+// stream operand after operand, not interleaved per chunk; the operands are
+// independent, and with one chunk the order is the same.
+inline void batched_ntt(fri_ctx* ctx, uint32_t lg, bool inv, const uint32_t* src, size_t len, uint32_t* dst,
+                        size_t np) {
+    NttPlan p = lde_plan(ctx, lg);
+    if (inv) p.tw = ctx->tw_inv;
+    p.src_stride = p.dst_stride = (size_t)1 << lg;
+    const size_t count = np >> lg;
+    for (size_t j0 = 0; j0 < count; j0 += 32768) {
+        p.batch = (uint32_t)(count - j0 < 32768 ? count - j0 : 32768);
+        launch_ntt(p, src + (j0 << lg), len, dst + (j0 << lg), ctx->stream);
+    }
+}
 // The inverse transform's post-scale N^-1 * R^r_pow: undoes the r_pow factors
-// of R^-1 a pointwise kernel left (fri_kernels.hip "polynomial arithmetic").
+// of R^-1 a pointwise kernel left (fri_poly_kernels.hip "polynomial arithmetic").
 inline uint32_t post_scale(uint32_t log_N, uint32_t r_pow) {
     uint32_t scale = inv_std((uint32_t)(((size_t)1 << log_N) % P));
     for (uint32_t i = 0; i < r_pow; i++) scale = mul_std(scale, R_MOD_P);
@@ -485,6 +503,41 @@ inline void inverse_with(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, cons
 inline void inverse(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, uint32_t r_pow, uint32_t* dst) {
     launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, 1u, post_scale(log_N, r_pow), ctx->stream);
     inverse_with(ctx, src, log_N, ctx->pow_lo, ctx->pow_hi, dst);
+}
+// Power-series inverse g = F^-1 mod x^K by Newton's iteration
+//   g <- g (2 - F g) mod x^m2,  m -> m2 = min(2m, K),
+// from a seed of m0 = min(K, 64) coefficients (below that a step would be four
+// launches on a handful of words).  F mod x^m2 times g times g has
+// m2 + 2m - 2 coefficients: no wrap-around at 2^log_N.
+struct NewtonStep { size_t m, m2; uint32_t log_N; };
+inline std::vector<NewtonStep> newton_steps(size_t K) {
+    std::vector<NewtonStep> steps;
+    for (size_t m = K < 64 ? K : 64; m < K;) {
+        const size_t m2 = 2 * m < K ? 2 * m : K;
+        steps.push_back({m, m2, ceil_log2(m2 + 2 * m - 2)});
+        m = m2;
+    }
+    return steps;
+}
+// Words of the buffer g grows in: a step's inverse transform lands in it whole.
+inline size_t series_words(const std::vector<NewtonStep>& steps, size_t K) {
+    return steps.empty() ? round4(K) : (size_t)1 << steps.back().log_N;
+}
+// Runs the steps on G, which holds the seed (enqueued by the caller); F has lf
+// words, both outside scratch_a / scratch_b.  inverse_step(k, src, log_N, G)
+// is step k's G = N^-1 R^2 iNTT(src): it writes over g, whose low m
+// coefficients come back unchanged; m..m2 are new, and nothing reads past m2
+// (the truncation).
+template <class InverseStep>
+inline void series_inverse(fri_ctx* ctx, const uint32_t* F, size_t lf, uint32_t* G,
+                           const std::vector<NewtonStep>& steps, InverseStep inverse_step) {
+    for (size_t k = 0; k < steps.size(); k++) {
+        const NewtonStep& st = steps[k];
+        forward(ctx, F, st.m2 < lf ? st.m2 : lf, st.log_N, ctx->scratch_a);
+        forward(ctx, G, st.m, st.log_N, ctx->scratch_b);
+        launch_poly_newton(ctx->scratch_a, ctx->scratch_b, ctx->scratch_a, (size_t)1 << st.log_N, ctx->stream);
+        inverse_step(k, ctx->scratch_a, st.log_N, G);
+    }
 }
 
 inline void digest_to_bytes(const uint32_t* w, uint8_t* out) {

@@ -1,5 +1,5 @@
 // fri_internal.hpp — device state layout and kernel launchers shared by
-// the kernel files (fri_kernels.hip, fri_layer.hip, ...) and the host code of
+// the kernel files (fri_kernels.hip, fri_poly_kernels.hip, fri_layer.hip, ...) and the host code of
 // the C ABI (fri_host.hpp and the files it lists).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -91,6 +91,8 @@ void launch_interp_eval(const uint32_t* xs, const uint32_t* c, size_t n, uint32_
 size_t evaluate_tmp_words(size_t d, size_t count);
 void launch_evaluate(const uint32_t* coeffs, size_t d, const uint32_t* xs, size_t count, uint32_t* out,
                      uint32_t* tmp, hipStream_t s);
+
+// ---- launchers (fri_poly_kernels.hip): the polynomial layer ---------------
 // Polynomial arithmetic (fri_poly.hip).  Pointwise on two transforms of n
 // canonical values: out = a*b*R^-1, and the Newton step out = g*(2 - f*g)*R^-2
 // (the caller's inverse transform scales by R or R^2, and N^-1); out may
@@ -150,6 +152,8 @@ void launch_mp_down_pointwise(const uint32_t* ta, uint32_t* tl, uint32_t* tr, si
 void launch_mp_take_high(const uint32_t* src, uint32_t* dst, size_t words, uint32_t lg, hipStream_t s);
 void launch_mp_up_pointwise(const uint32_t* fl, const uint32_t* fr, const uint32_t* bl, const uint32_t* br,
                             uint32_t* out, size_t words, uint32_t lg, hipStream_t s);
+
+// ---- launchers (fri_kernels.hip): decommitment gather, standalone fold ----
 struct DecommitPlan {
     uint64_t index;
     uint32_t log_n, n_layers;

@@ -27,18 +27,10 @@ struct Layout {
     size_t np = 0;
     size_t xs = 0, lev = 0, F = 0, G = 0, f = 0, rf = 0, a0 = 0, a1 = 0, end = 0;
     uint32_t levels() const { return log_np - lf_log + 1; }
+    // the retained level of nodes of degree 2^lg, lf_log <= lg <= log_np (np
+    // words; the children of a product of 2^lg words are level lg - 1)
+    size_t level(uint32_t lg) const { return lev + (size_t)(lg - lf_log) * np; }
 };
-// The Newton steps of g = F^-1 mod x^K: m -> min(2m, K) from m = min(K, 64),
-// as in fri_poly_div_rem; the largest inverse transform lands in g whole.
-size_t series_words(size_t K) {
-    size_t w = round4(K);
-    for (size_t m = K < 64 ? K : 64; m < K;) {
-        const size_t m2 = 2 * m < K ? 2 * m : K;
-        w = (size_t)1 << ceil_log2(m2 + 2 * m - 2);
-        m = m2;
-    }
-    return w;
-}
 // count points, a polynomial of d coefficients (0: none uploaded or reversed)
 Layout layout(fri_ctx* ctx, size_t count, size_t d, bool small_leaf, size_t base) {
     Layout L;
@@ -50,7 +42,7 @@ Layout layout(fri_ctx* ctx, size_t count, size_t d, bool small_leaf, size_t base
     L.lev = L.xs + round4(count);
     L.F = L.lev + round4(L.levels() * L.np + 1);  // the top level is followed by Z_pad's leading 1
     L.G = L.F + round4(L.np + 1);
-    L.f = L.G + series_words(d);
+    L.f = L.G + series_words(newton_steps(d), d);
     L.rf = L.f + round4(d);
     L.a0 = L.rf + round4(d);
     L.a1 = L.a0 + round4(L.np);
@@ -63,19 +55,10 @@ bool eval_fits(const fri_ctx* ctx, size_t d, size_t count) {
     return d <= cap && np <= cap && d + np - 1 <= cap && ((size_t)2 << ceil_log2(d)) <= cap;
 }
 
-NttPlan batched(fri_ctx* ctx, uint32_t lg, bool inv, size_t pairs, size_t p0) {
-    NttPlan p{};
-    p.log_n = lg;
-    p.tw = inv ? ctx->tw_inv : ctx->tw_fwd;
-    p.batch = (uint32_t)(pairs - p0 < 32768 ? pairs - p0 : 32768);
-    p.src_stride = p.dst_stride = (size_t)1 << lg;
-    return p;
-}
-
 int build_tree(fri_ctx* ctx, const Layout& L, size_t count) {
     uint32_t* t = ctx->interp_tmp;
     product_tree(ctx, t + L.xs, count, L.lf_log, t + L.lev);
-    FRI_HIP(ctx, hipMemcpyAsync(t + L.lev + (size_t)L.levels() * L.np, &ONE, 4, hipMemcpyHostToDevice, ctx->stream));
+    FRI_HIP(ctx, hipMemcpyAsync(t + L.level(L.log_np) + L.np, &ONE, 4, hipMemcpyHostToDevice, ctx->stream));
     return FRI_OK;
 }
 
@@ -86,21 +69,13 @@ void evaluate_on_tree(fri_ctx* ctx, const Layout& L, const uint32_t* f, size_t d
     hipStream_t s = ctx->stream;
     uint32_t* t = ctx->interp_tmp;
     const size_t np = L.np;
-    const uint32_t* top = t + L.lev + (size_t)(L.levels() - 1) * np;
     uint32_t *F = t + L.F, *G = t + L.G, *a = t + L.a0, *b = t + L.a1;
-    launch_poly_reverse(top, np, np + 1, F, np + 1, s);            // rev(Z_pad): F[0] = 1
-    // g = F^-1 mod x^d.  Newton: g <- g (2 - F g) mod x^m2, as in fri_poly_div_rem
-    size_t m = d < 64 ? d : 64;
-    launch_mp_series_seed(F, np + 1, (uint32_t)m, G, s);
-    while (m < d) {
-        const size_t m2 = 2 * m < d ? 2 * m : d;
-        const uint32_t log_N = ceil_log2(m2 + 2 * m - 2);
-        forward(ctx, F, m2 < np + 1 ? m2 : np + 1, log_N, ctx->scratch_a);
-        forward(ctx, G, m, log_N, ctx->scratch_b);
-        launch_poly_newton(ctx->scratch_a, ctx->scratch_b, ctx->scratch_a, (size_t)1 << log_N, s);
-        inverse(ctx, ctx->scratch_a, log_N, 2, G);
-        m = m2;
-    }
+    launch_poly_reverse(t + L.level(L.log_np), np, np + 1, F, np + 1, s);   // rev(Z_pad): F[0] = 1
+    // g = F^-1 mod x^d
+    launch_mp_series_seed(F, np + 1, (uint32_t)(d < 64 ? d : 64), G, s);
+    series_inverse(ctx, F, np + 1, G, newton_steps(d), [&](size_t, const uint32_t* src, uint32_t log_N, uint32_t* dst) {
+        inverse(ctx, src, log_N, 2, dst);
+    });
     // the root vector: the d + np - 1 wide cyclic product keeps the wrap off
     // the np coefficients read
     {
@@ -113,32 +88,24 @@ void evaluate_on_tree(fri_ctx* ctx, const Layout& L, const uint32_t* f, size_t d
         launch_poly_reverse(ctx->scratch_c, d - 1, d < np ? d : np, a, np, s);
     }
     for (uint32_t lg = L.log_np; lg > L.lf_log; lg--) {             // parents of 2^lg words -> children
-        const uint32_t* nodes = t + L.lev + (size_t)(lg - 1 - L.lf_log) * np;
+        const uint32_t* nodes = t + L.level(lg - 1);
         if (lg <= ROOTS_LDS_LOG_MAX) {
             launch_mp_down_level_lds(a, nodes, b, L.log_np, lg, ctx->tw_fwd, ctx->tw_inv, s);
             std::swap(a, b);
             continue;
         }
-        const size_t m2 = (size_t)1 << lg, h = m2 >> 1, pairs = np >> lg;
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            const NttPlan p = batched(ctx, lg, false, pairs, p0);
-            launch_ntt(p, a + off, m2, ctx->scratch_a + off, s);
-            launch_ntt(p, nodes + off, h, ctx->scratch_b + off, s);
-            launch_ntt(p, nodes + off + h, h, ctx->scratch_c + off, s);
-        }
+        const size_t m2 = (size_t)1 << lg, h = m2 >> 1;
+        batched_ntt(ctx, lg, false, a, m2, ctx->scratch_a, np);
+        batched_ntt(ctx, lg, false, nodes, h, ctx->scratch_b, np);
+        batched_ntt(ctx, lg, false, nodes + h, h, ctx->scratch_c, np);
         launch_mp_down_pointwise(ctx->scratch_a, ctx->scratch_b, ctx->scratch_c, np, lg, s);
         // a_R lands in place; a_L's product goes through the old level's buffer
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            const NttPlan p = batched(ctx, lg, true, pairs, p0);
-            launch_ntt(p, ctx->scratch_b + off, m2, b + off, s);
-            launch_ntt(p, ctx->scratch_c + off, m2, a + off, s);
-        }
+        batched_ntt(ctx, lg, true, ctx->scratch_b, m2, b, np);
+        batched_ntt(ctx, lg, true, ctx->scratch_c, m2, a, np);
         launch_mp_take_high(a, b, np, lg, s);
         std::swap(a, b);
     }
-    launch_mp_leaf_eval(t + L.xs, count, t + L.lev, L.lf_log == L.log_np, a, L.log_np, L.lf_log, out, s);
+    launch_mp_leaf_eval(t + L.xs, count, t + L.level(L.lf_log), L.lf_log == L.log_np, a, L.log_np, L.lf_log, out, s);
 }
 
 int check_flags(fri_ctx* ctx, uint32_t flags) {
@@ -224,7 +191,7 @@ extern "C" int fri_interpolate_points_ex(fri_ctx* ctx, const uint32_t* xs, const
     FRI_HIP(ctx, hipMemcpyAsync(t + L.xs, xs, n * 4, hipMemcpyHostToDevice, s));
     FRI_HIP(ctx, hipMemcpyAsync(t + oY, ys, n * 4, hipMemcpyHostToDevice, s));
     if (const int rt = build_tree(ctx, L, n)) return rt;
-    const uint32_t* z = t + L.lev + (size_t)(L.levels() - 1) * np + (np - n);   // Z's n low coefficients
+    const uint32_t* z = t + L.level(log_N) + (np - n);              // Z's n low coefficients
     launch_mp_derivative(z, n, t + oD, s);
     evaluate_on_tree(ctx, L, t + oD, n, n, t + oV);                // Z'(x_i) = prod_{j!=i}(x_i - x_j)
     launch_batch_inverse(t + oV, t + oC, n, 1, s);                  // w_i (Montgomery; 0 -> 0)
@@ -232,26 +199,19 @@ extern "C" int fri_interpolate_points_ex(fri_ctx* ctx, const uint32_t* xs, const
     uint32_t *F = t + L.a0, *Fn = t + L.a1;
     launch_mp_leaf_up(t + L.xs, t + oC, n, log_N, L.lf_log, F, s);
     for (uint32_t lg = L.lf_log + 1; lg <= log_N; lg++) {           // children of 2^(lg-1) words -> parents
-        const uint32_t* nodes = t + L.lev + (size_t)(lg - 1 - L.lf_log) * np;
+        const uint32_t* nodes = t + L.level(lg - 1);
         if (lg <= ROOTS_LDS_LOG_MAX) {
             launch_mp_up_level_lds(F, nodes, Fn, log_N, lg, ctx->tw_fwd, ctx->tw_inv, s);
             std::swap(F, Fn);
             continue;
         }
-        const size_t h = (size_t)1 << (lg - 1), pairs = np >> lg;
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            const NttPlan p = batched(ctx, lg, false, pairs, p0);
-            launch_ntt(p, F + off, h, ctx->scratch_a + off, s);
-            launch_ntt(p, F + off + h, h, ctx->scratch_b + off, s);
-            launch_ntt(p, nodes + off, h, ctx->scratch_c + off, s);
-            launch_ntt(p, nodes + off + h, h, t + oT + off, s);
-        }
+        const size_t h = (size_t)1 << (lg - 1);
+        batched_ntt(ctx, lg, false, F, h, ctx->scratch_a, np);
+        batched_ntt(ctx, lg, false, F + h, h, ctx->scratch_b, np);
+        batched_ntt(ctx, lg, false, nodes, h, ctx->scratch_c, np);
+        batched_ntt(ctx, lg, false, nodes + h, h, t + oT, np);
         launch_mp_up_pointwise(ctx->scratch_a, ctx->scratch_b, ctx->scratch_c, t + oT, ctx->scratch_a, np, lg, s);
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            launch_ntt(batched(ctx, lg, true, pairs, p0), ctx->scratch_a + off, (size_t)1 << lg, Fn + off, s);
-        }
+        batched_ntt(ctx, lg, true, ctx->scratch_a, (size_t)1 << lg, Fn, np);
         std::swap(F, Fn);
     }
     FRI_HIP(ctx, hipGetLastError());

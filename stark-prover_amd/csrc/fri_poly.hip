@@ -20,22 +20,18 @@ namespace {
 // whole call instead of one table launch per transform: every table has base
 // 1, so the low level (Montgomery(1) throughout, ctx->pow_lo) is shared, and a
 // transform's high level is max(1, N / 2^POW_LO_LOG) copies of
-// Montgomery(N^-1 * R^r_pow), uploaded together in the order of use.
+// Montgomery(N^-1 * R^r_pow), uploaded together.
 struct PostScales {
     std::vector<uint32_t> host;
-    std::vector<std::pair<uint32_t, size_t>> order;   // (log_N, offset in host)
+    std::vector<size_t> offset;                       // of the i-th planned table in host
     const uint32_t* dev = nullptr;
-    size_t used = 0;
-    void plan(uint32_t log_N, uint32_t r_pow) {
-        order.emplace_back(log_N, host.size());
+    size_t plan(uint32_t log_N, uint32_t r_pow) {     // returns the table's index
+        offset.push_back(host.size());
         const size_t nhi = log_N > POW_LO_LOG ? (size_t)1 << (log_N - POW_LO_LOG) : 1;
         host.insert(host.end(), nhi, to_mont(post_scale(log_N, r_pow)));
+        return offset.size() - 1;
     }
-    // the next planned transform's high level; nullptr if the call order drifted from the plan
-    const uint32_t* take(uint32_t log_N) {
-        if (used >= order.size() || order[used].first != log_N) return nullptr;
-        return dev + order[used++].second;
-    }
+    const uint32_t* table(size_t i) const { return dev + offset[i]; }
 };
 // scratch_c[0..2^log_N) = x * y (cyclic, size 2^log_N); x and y anywhere but
 // scratch_a / scratch_b.
@@ -125,32 +121,20 @@ extern "C" int fri_poly_div_rem(fri_ctx* ctx, const uint32_t* a, size_t la, cons
         return fail(ctx, FRI_EINVAL, "output capacity too small (needed lengths in *q_len, *r_len: la-lb+1, lb-1)");
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // the transforms of the call, in order: the Newton steps m -> m2 = min(2m, K)
-    // from m = min(K, 64), the quotient product, the remainder product
-    const size_t m0 = K < 64 ? K : 64;
+    // the inverse transforms of the call and their post-scale tables: Newton
+    // step k's is table k, then the quotient product's, the remainder product's
+    const std::vector<NewtonStep> steps = newton_steps(K);
     const size_t lq_r = K < nr ? K : nr;                           // q and b cut to the low nr coefficients
     const bool r_direct = lq_r <= FRI_POLY_DIRECT_MAX;
+    const uint32_t log_Q = ceil_log2(2 * K - 1), log_R = nr ? ceil_log2(lq_r + nr - 1) : 0;
     PostScales ps;
-    // (cannot happen: the loops below repeat the plan's arithmetic; the host
-    // buffers of the uploads already enqueued must outlive them, hence the wait)
-    auto drifted = [&]() {
-        (void)hipStreamSynchronize(s);
-        return fail(ctx, FRI_EHIP, "division: transform schedule differs from its plan");
-    };
-    size_t g_words = round4(K);
-    for (size_t m = m0; m < K;) {
-        const size_t m2 = 2 * m < K ? 2 * m : K;
-        const uint32_t log_N = ceil_log2(m2 + 2 * m - 2);
-        ps.plan(log_N, 2);
-        g_words = (size_t)1 << log_N;                              // the step's iNTT writes g in place
-        m = m2;
-    }
-    ps.plan(ceil_log2(2 * K - 1), 1);
-    if (nr && !r_direct) ps.plan(ceil_log2(lq_r + nr - 1), 1);
+    for (const NewtonStep& st : steps) ps.plan(st.log_N, 2);
+    const size_t ps_q = ps.plan(log_Q, 1);
+    const size_t ps_r = nr && !r_direct ? ps.plan(log_R, 1) : 0;
     // operands and the running results live in the partials scratch; the three
     // context buffers are the transforms' work space
-    const size_t oA = 0, oB = oA + round4(la), oF = oB + round4(lb), oG = oF + round4(lb), oQ = oG + g_words,
-                 oS = oQ + round4(K);
+    const size_t oA = 0, oB = oA + round4(la), oF = oB + round4(lb), oG = oF + round4(lb),
+                 oQ = oG + series_words(steps, K), oS = oQ + round4(K);
     const int rc = ensure_tmp(ctx, oS + ps.host.size());
     if (rc) return rc;
     uint32_t* A = ctx->interp_tmp + oA;
@@ -166,38 +150,21 @@ extern "C" int fri_poly_div_rem(fri_ctx* ctx, const uint32_t* a, size_t la, cons
     launch_poly_reverse(B, lb - 1, lb, F, lb, s);
     // g mod x^m0 by the power-series recurrence on the host (m0 <= 64: the
     // Newton steps below would each be four launches on a handful of words)
-    size_t m = m0;
+    const size_t m0 = K < 64 ? K : 64;
     uint32_t g0[64];
     g0[0] = inv_std(b[lb - 1]);
-    for (size_t i = 1; i < m; i++) {
+    for (size_t i = 1; i < m0; i++) {
         uint64_t acc = 0;
         for (size_t j = 1; j <= i && j < lb; j++) acc = (acc + (uint64_t)b[lb - 1 - j] * g0[i - j] % P) % P;
         g0[i] = (uint32_t)((uint64_t)(P - (uint32_t)acc) % P * g0[0] % P);
     }
-    FRI_HIP(ctx, hipMemcpyAsync(G, g0, m * 4, hipMemcpyHostToDevice, s));
-    // Newton: g <- g (2 - f g) mod x^m2, m2 = min(2m, K).  f mod x^m2 times g
-    // times g has m2 + 2m - 2 coefficients: no wrap-around at that size.
-    while (m < K) {
-        const size_t m2 = 2 * m < K ? 2 * m : K;
-        const uint32_t log_N = ceil_log2(m2 + 2 * m - 2);
-        const uint32_t* hi = ps.take(log_N);
-        if (!hi) return drifted();
-        forward(ctx, F, m2 < lb ? m2 : lb, log_N, ctx->scratch_a);
-        forward(ctx, G, m, log_N, ctx->scratch_b);
-        launch_poly_newton(ctx->scratch_a, ctx->scratch_b, ctx->scratch_a, (size_t)1 << log_N, s);
-        // the iNTT writes over g: the low m coefficients come back unchanged,
-        // m..m2 are new, and nothing reads past m2 (the truncation)
-        inverse_with(ctx, ctx->scratch_a, log_N, ctx->pow_lo, hi, G);
-        m = m2;
-    }
+    FRI_HIP(ctx, hipMemcpyAsync(G, g0, m0 * 4, hipMemcpyHostToDevice, s));
+    series_inverse(ctx, F, lb, G, steps, [&](size_t k, const uint32_t* src, uint32_t log_N, uint32_t* dst) {
+        inverse_with(ctx, src, log_N, ctx->pow_lo, ps.table(k), dst);
+    });
     // q = rev((rev(a) mod x^K) * g mod x^K)
     launch_poly_reverse(A, la - 1, K, Q, K, s);
-    {
-        const uint32_t log_N = ceil_log2(2 * K - 1);
-        const uint32_t* hi = ps.take(log_N);
-        if (!hi) return drifted();
-        product(ctx, Q, K, G, K, log_N, hi);
-    }
+    product(ctx, Q, K, G, K, log_Q, ps.table(ps_q));
     launch_poly_reverse(ctx->scratch_c, K - 1, K, Q, K, s);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(q_out, Q, K * 4, hipMemcpyDeviceToHost, s));
@@ -206,10 +173,7 @@ extern "C" int fri_poly_div_rem(fri_ctx* ctx, const uint32_t* a, size_t la, cons
         if (r_direct) {
             launch_poly_conv_direct(B, nr, Q, lq_r, ctx->scratch_c, nr, s);
         } else {
-            const uint32_t log_N = ceil_log2(lq_r + nr - 1);
-            const uint32_t* hi = ps.take(log_N);
-            if (!hi) return drifted();
-            product(ctx, Q, lq_r, B, nr, log_N, hi);
+            product(ctx, Q, lq_r, B, nr, log_R, ps.table(ps_r));
         }
         launch_poly_sub(A, ctx->scratch_c, ctx->scratch_b, nr, s);
         FRI_HIP(ctx, hipGetLastError());

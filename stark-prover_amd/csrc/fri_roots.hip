@@ -49,28 +49,12 @@ const uint32_t* product_tree(fri_ctx* ctx, const uint32_t* d_roots, size_t n, ui
         }
         // even nodes -> x, odd nodes -> y, each zero-padded to 2^lg and
         // transformed; the product's inverse transform lands in cur again.
-        // (A launch carries at most 2^15 transforms: more than one chunk only
-        // beyond 2^28 roots.)
-        const size_t two_m = (size_t)1 << lg, m = two_m >> 1, pairs = np >> lg;
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            NttPlan f = lde_plan(ctx, lg);
-            f.batch = (uint32_t)(pairs - p0 < 32768 ? pairs - p0 : 32768);
-            f.src_stride = f.dst_stride = two_m;
-            launch_ntt(f, cur + off, m, x + off, s);
-            launch_ntt(f, cur + off + m, m, y + off, s);
-        }
+        const size_t two_m = (size_t)1 << lg, m = two_m >> 1;
+        batched_ntt(ctx, lg, false, cur, m, x, np);
+        batched_ntt(ctx, lg, false, cur + m, m, y, np);
         launch_roots_pointwise(x, y, x, np, lg, top, s);
         if (keep) cur = kept;
-        for (size_t p0 = 0; p0 < pairs; p0 += 32768) {
-            const size_t off = p0 << lg;
-            NttPlan b{};
-            b.log_n = lg;
-            b.tw = ctx->tw_inv;
-            b.batch = (uint32_t)(pairs - p0 < 32768 ? pairs - p0 : 32768);
-            b.src_stride = b.dst_stride = two_m;
-            launch_ntt(b, x + off, two_m, cur + off, s);
-        }
+        batched_ntt(ctx, lg, true, x, two_m, cur, np);
     }
     return cur + (np - n);
 }
