@@ -525,6 +525,76 @@ int fri_batch_commit_degrees(fri_ctx* ctx, uint32_t member, int32_t* out, size_t
 int fri_batch_decommit_query(fri_ctx* ctx, uint32_t member, uint64_t index, uint32_t* values, size_t values_cap,
                              uint8_t* paths, size_t paths_cap, size_t* paths_len);
 
+/* Batched prover: `batch` STARK-101 FibonacciSq proofs of one shape
+ * (log_t, log_blowup, offset), each with its own trace and channel, in a
+ * fixed number of launches per step instead of per proof.  Every member's
+ * results are bit-identical to fri_trace_commit, fri_fibsq_composition_commit,
+ * fri_trace_decommit and fri_decommit_query for the same inputs.
+ *
+ * L = log_t + log_blowup with 1 <= L <= FRI_BATCH_MAX_LOG_N (and the context's
+ * log_n_max), log_t >= 2, log_blowup in 1..4, 1 <= batch <= 65535; one-device
+ * contexts only (a multi-GPU context gives FRI_EINVAL, a profiling context
+ * FRI_ESTATE, as fri_commit_batch).  A value that is not canonical, a shape
+ * outside the limits or an offset with offset^T in <w_B> is FRI_EINVAL for the
+ * whole call (the message names the member) and nothing is written.
+ *
+ * fri_trace_commit_batch: batch x fri_trace_commit.  traces: batch * 2^log_t
+ * canonical words (host), roots32: batch * 32 bytes.  The LDEs and trees stay
+ * resident in the batch's buffers (4 * 2^L + 64 * 2^L bytes per member, and
+ * 8 * 2^log_t more for the input and the coefficients) through the composition
+ * commit that consumes them, until the next fri_trace_commit_batch, any
+ * non-batch commit, a plain fri_commit_batch or fri_ctx_destroy; the single
+ * fri_trace_commit's resident trace is not touched.  FRI_ENOMEM leaves the
+ * context usable and what was resident readable.
+ *   How it runs: the interpolation on <w_T> in LDS up to 2^12 (one workgroup
+ * per member), above that the batched transform; the LDE of fri_commit_batch;
+ * then ONE launch hashes every member's tree, one 512-thread workgroup each.
+ *
+ * fri_fibsq_composition_commit_batch: batch x fri_fibsq_composition_commit on
+ * the resident trace batch (same log_t, log_blowup, offset and batch, else
+ * FRI_ESTATE).  a_last[b], alphas[3*b .. 3*b+2], chan_in[b] (required),
+ * out[b], status[b].  flags: FRI_FLAG_NO_GRAPH is accepted without effect,
+ * anything else is FRI_EINVAL.  The composition's coefficients are committed
+ * as fri_commit_batch_device commits them (the commit generation moves, the
+ * fri_batch_* read-backs serve the members).  A member whose composition
+ * polynomial has degree above 2^log_t (its trace violates the constraints)
+ * gets status[b] = FRI_EDEGREE and serves no read-backs; every other member
+ * is served, and the call returns the first failing member's code.
+ *
+ * fri_batch_query_round: one query of every member of the resident batch in
+ * ONE launch and ONE read-back.  indices[b]: member b's query index (taken
+ * mod each layer's size, as fri_decommit_query; < 2^L when trace_count > 0).
+ * skip (may be NULL): skip[b] != 0 leaves member b out; so is a member whose
+ * commit failed.  trace_count = 0: the FRI openings only (serves a plain
+ * fri_commit_batch); trace_count 1..8 needs the resident trace batch behind
+ * the batch (else FRI_ESTATE) and opens LDE[(index + j*trace_stride) mod 2^L],
+ * j < trace_count, with their paths.  Member b's record:
+ *   values + b*values_stride (words): trace_count trace values, then
+ *     2 * n_layers(b) FRI values in fri_decommit_query's order;
+ *   paths + b*paths_stride (bytes): trace_count paths of 32*L bytes, then the
+ *     FRI paths in fri_decommit_query's layout;
+ *   paths_len[b]: the bytes written (0 for a member left out, whose record is
+ *     not touched).
+ * Strides too small for the served member with the most layers give
+ * FRI_EINVAL with the needed paths_stride in paths_len[0]; the needed
+ * values_stride is trace_count + 2 * n_layers words.
+ *
+ * Measured against a loop of prove_fibsq through the Python mirror
+ * (tools/batch_probe.py --prove, profiles/prove_batch.txt, DESIGN.md section
+ * 4f; us per proof inside the device calls, blowup 8, B = 256): 8.8 against
+ * 827 at log_t 7 with 8 queries, 22.7 against 1788 with 32; 76.1 against 1320
+ * and 96.9 against 2428 at log_t 13.  The batch is faster from the smallest
+ * size measured, B = 16, at every measured shape (1.4x at log_t 13, 8 queries). */
+int fri_trace_commit_batch(fri_ctx* ctx, const uint32_t* traces, uint32_t log_t, uint32_t log_blowup,
+                           uint32_t offset, uint32_t batch, uint8_t* roots32);
+int fri_fibsq_composition_commit_batch(fri_ctx* ctx, uint32_t log_t, uint32_t log_blowup, uint32_t offset,
+                                       uint32_t batch, const uint32_t* a_last, const uint32_t* alphas,
+                                       const fri_channel_state* chan_in, uint32_t flags, fri_commit_result* out,
+                                       int* status);
+int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* skip, uint32_t trace_count,
+                          uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
+                          size_t paths_stride, size_t* paths_len);
+
 /* Which commit the read-backs below serve: `generation` grows with every
  * commit call on the context (successful or not), log_n / n_layers describe
  * the resident commit (n_layers = 0 when the last commit failed).  A binding

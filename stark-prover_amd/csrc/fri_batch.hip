@@ -4,6 +4,9 @@
 // workgroup per member (k_commit_batch, fri_layer.hip).  The batch has its
 // own buffers (Batch, fri_host.hpp): no lane's plan or graph is touched, so a
 // single commit afterwards replays what it captured.  Member-wise read-backs.
+// Below them the batched prover: B x fri_trace_commit, B x
+// fri_fibsq_composition_commit on that trace batch, and one query of every
+// member in one launch (fri_batch_query_round).
 #include "fri_host.hpp"
 
 static_assert(FRI_BATCH_MAX_LOG_N >= 14 && FRI_BATCH_MAX_LOG_N <= (int)BATCH_MAX_LOG, "the kernel's tiles");
@@ -19,6 +22,7 @@ void fri::batch_free(fri_ctx* ctx) {
     Batch& B = ctx->batch;
     bufs_release(ctx, B.b);
     dfree(ctx, B.xinv); dfree(ctx, B.pre_lo); dfree(ctx, B.pre_hi);
+    if (B.h_q) hipHostFree(B.h_q);
     B = Batch();
 }
 
@@ -87,31 +91,88 @@ static int batch_tables(fri_ctx* ctx, uint32_t log_n, uint32_t offset) {
     return FRI_OK;
 }
 
-static int run_batch(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* dev_coeffs, size_t d, uint32_t batch,
-                     uint32_t log_n, uint32_t offset, const fri_channel_state* chan_in, uint32_t flags,
-                     const uint32_t* forced_betas, fri_commit_result* out, int* status) {
-    if (!ctx || !out || !status) return fail(ctx, FRI_EINVAL, "null argument");
-    if (d && !host_coeffs && !dev_coeffs) return fail(ctx, FRI_EINVAL, "null coefficients");
+// Batches run on one-device contexts, outside profiling.
+static int batch_ctx_ok(fri_ctx* ctx) {
     if (ctx->team_root || ctx->tp.team)
         return fail(ctx, FRI_EINVAL, "multi-GPU context: batched commits run on one-device contexts");
     if (ctx->profiling) return fail(ctx, FRI_ESTATE, "profiling: time commits with fri_commit_device");
-    if (flags & ~(FRI_FLAG_FORCE_BETAS | FRI_FLAG_NO_GRAPH))
-        return fail(ctx, FRI_EINVAL, "fri_commit_batch takes FRI_FLAG_FORCE_BETAS and FRI_FLAG_NO_GRAPH only");
-    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
-    if (log_n > FRI_BATCH_MAX_LOG_N) return fail(ctx, FRI_EINVAL, "log_n above FRI_BATCH_MAX_LOG_N");
-    int rc = commit_validate(ctx, d, log_n, offset, 0u, nullptr);
-    if (rc) return rc;
-    const bool forced = (flags & FRI_FLAG_FORCE_BETAS) != 0;
-    if (forced && !forced_betas) return fail(ctx, FRI_EINVAL, "forced betas missing");
-    if (forced && !check_canonical(forced_betas, (size_t)batch * MAXR))
-        return fail(ctx, FRI_EINVAL, "forced beta not canonical");
-    FRI_HIP(ctx, hipSetDevice(ctx->device));
-    // pending pipelined commits first, on whichever lane (the tables below use the context's scratch)
+    return FRI_OK;
+}
+
+// Pending pipelined commits first, on whichever lane (the batch's tables use the context's scratch).
+static int batch_quiesce(fri_ctx* ctx) {
     settle(ctx);
     FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (Lane& ln : ctx->lanes)
         if (ln.stream) FRI_HIP(ctx, hipStreamSynchronize(ln.stream));
     ctx->async_unsettled = false;
+    return FRI_OK;
+}
+
+// The members' LDE on offset * <w_n> (batch_tables' powers): member b's d
+// coefficients at src + b * src_stride into dst + b * dst_stride, a fixed
+// number of launches.  Above the LDS transform it goes through BB_SCALED
+// (batch * round4(d) words).
+static void batch_lde(fri_ctx* ctx, const uint32_t* src, size_t src_stride, size_t d, uint32_t* dst, size_t dst_stride,
+                      uint32_t log_n, uint32_t batch, hipStream_t s) {
+    Batch& B = ctx->batch;
+    if (log_n <= BATCH_LDS_LDE_MAX_LOG) {
+        launch_batch_lde_lds(src, src_stride, d, dst, dst_stride, log_n, batch, ctx->tw_fwd, B.pre_lo, B.pre_hi, s);
+        return;
+    }
+    const size_t sc_stride = round4(d);
+    uint32_t* scaled = B.b.words(BB_SCALED);
+    launch_batch_scale(src, src_stride, scaled, sc_stride, d, batch, B.pre_lo, B.pre_hi, s);
+    NttPlan np = lde_plan(ctx, log_n);
+    np.batch = batch;
+    np.src_stride = sc_stride;
+    np.dst_stride = dst_stride;
+    launch_ntt(np, scaled, d, dst, s);
+}
+
+// The members' coset interpolation: dst_b[j] = 2^-lg base^j sum_i src_b[i] w^-ij,
+// j < 2^lg (strides in words, multiples of 4 above the LDS transform).  The
+// post-scale table is the context's (pow_lo / pow_hi), made on the stream.
+static void batch_intt(fri_ctx* ctx, const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride,
+                       uint32_t lg, uint32_t batch, uint32_t base, hipStream_t s) {
+    launch_pow_table(ctx->pow_lo, ctx->pow_hi, lg, base, inv_std((uint32_t)(((size_t)1 << lg) % P)), s);
+    if (lg <= BATCH_LDS_LDE_MAX_LOG) {
+        launch_batch_intt_lds(src, src_stride, dst, dst_stride, lg, batch, ctx->tw_inv, ctx->pow_lo, ctx->pow_hi, s);
+        return;
+    }
+    NttPlan ip{};
+    ip.log_n = lg;
+    ip.tw = ctx->tw_inv;
+    ip.post_lo = ctx->pow_lo;
+    ip.post_hi = ctx->pow_hi;
+    ip.batch = batch;
+    ip.src_stride = src_stride;
+    ip.dst_stride = dst_stride;
+    launch_ntt(ip, src, (size_t)1 << lg, dst, s);
+}
+
+// keep_trace: the commit of a resident trace batch's composition (the trace
+// batch stays); deg0_max != 0: a member whose input has a larger degree fails
+// with FRI_EDEGREE (the composition of a trace that violates its constraints).
+static int run_batch(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* dev_coeffs, size_t d, uint32_t batch,
+                     uint32_t log_n, uint32_t offset, const fri_channel_state* chan_in, uint32_t flags,
+                     const uint32_t* forced_betas, fri_commit_result* out, int* status, bool keep_trace = false,
+                     uint32_t deg0_max = 0) {
+    if (!ctx || !out || !status) return fail(ctx, FRI_EINVAL, "null argument");
+    if (d && !host_coeffs && !dev_coeffs) return fail(ctx, FRI_EINVAL, "null coefficients");
+    int rc = batch_ctx_ok(ctx);
+    if (rc) return rc;
+    if (flags & ~(FRI_FLAG_FORCE_BETAS | FRI_FLAG_NO_GRAPH))
+        return fail(ctx, FRI_EINVAL, "fri_commit_batch takes FRI_FLAG_FORCE_BETAS and FRI_FLAG_NO_GRAPH only");
+    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
+    if (log_n > FRI_BATCH_MAX_LOG_N) return fail(ctx, FRI_EINVAL, "log_n above FRI_BATCH_MAX_LOG_N");
+    if ((rc = commit_validate(ctx, d, log_n, offset, 0u, nullptr))) return rc;
+    const bool forced = (flags & FRI_FLAG_FORCE_BETAS) != 0;
+    if (forced && !forced_betas) return fail(ctx, FRI_EINVAL, "forced betas missing");
+    if (forced && !check_canonical(forced_betas, (size_t)batch * MAXR))
+        return fail(ctx, FRI_EINVAL, "forced beta not canonical");
+    FRI_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = batch_quiesce(ctx))) return rc;
 
     Batch& B = ctx->batch;
     Plan lay;
@@ -137,6 +198,7 @@ static int run_batch(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* 
     ctx->res_lane = ctx->cur_lane;
     ctx->sharded_layers = 0;
     B.resident = true;
+    if (!keep_trace) B.trace_resident = false;
     B.count = batch;
     B.log_n = log_n;
     B.lay = lay;
@@ -160,16 +222,8 @@ static int run_batch(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* 
     uint32_t* layers = B.b.words(BB_LAYERS);
     if (!d) {
         FRI_HIP(ctx, hipMemsetAsync(layers, 0, batch * lay_stride * 4, s));
-    } else if (lds_lde) {
-        launch_batch_lde_lds(src, d, d, layers, lay_stride, log_n, batch, ctx->tw_fwd, B.pre_lo, B.pre_hi, s);
     } else {
-        uint32_t* scaled = B.b.words(BB_SCALED);
-        launch_batch_scale(src, d, scaled, sc_stride, d, batch, B.pre_lo, B.pre_hi, s);
-        NttPlan np = lde_plan(ctx, log_n);
-        np.batch = batch;
-        np.src_stride = sc_stride;
-        np.dst_stride = lay_stride;
-        launch_ntt(np, scaled, d, layers, s);
+        batch_lde(ctx, src, d, d, layers, lay_stride, log_n, batch, s);
     }
     // ---- every member's commit: one launch ----
     BatchTask bt{};
@@ -200,13 +254,26 @@ static int run_batch(fri_ctx* ctx, const uint32_t* host_coeffs, const uint32_t* 
 
     int first = FRI_OK;
     uint32_t first_b = 0;
+    bool first_degree = false, degree_b = false;
     for (uint32_t b = 0; b < batch; b++) {
         memset(&out[b], 0, sizeof out[b]);
         status[b] = commit_finish(ctx, &hs[b], log_n, &out[b]);     // (a failed member serves nothing: n_layers = 0)
-        if (status[b] && !first) { first = status[b]; first_b = b; }
+        if (!status[b] && deg0_max && hs[b].deg[0] > (int32_t)deg0_max) {
+            status[b] = FRI_EDEGREE;
+            hs[b].status = FRI_EDEGREE;
+            hs[b].n_layers = 0;          // no proof of a violated trace is served
+            memset(&out[b], 0, sizeof out[b]);
+            degree_b = true;
+        } else {
+            degree_b = false;
+        }
+        if (status[b] && !first) { first = status[b]; first_b = b; first_degree = degree_b; }
     }
     if (first)
-        return fail(ctx, first, "member " + std::to_string(first_b) + ": " + status_message((uint32_t)first));
+        return fail(ctx, first,
+                    "member " + std::to_string(first_b) + ": " +
+                        (first_degree ? "composition polynomial degree exceeds T: the trace violates the constraints"
+                                      : status_message((uint32_t)first)));
     return FRI_OK;
 }
 
@@ -328,5 +395,249 @@ extern "C" int fri_batch_decommit_query(fri_ctx* ctx, uint32_t member, uint64_t 
     FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(values, ctx->dq_host, 2 * dp.n_layers * 4);
     memcpy(paths, ctx->dq_host + 2 * dp.n_layers, (size_t)words * 4);
+    return FRI_OK;
+}
+
+// ------------------------------------------------------ batched prover ----
+// B proofs of one shape (log_t, log_blowup, offset): what fri_trace_commit,
+// fri_fibsq_composition_commit and the per-query read-backs do for one proof,
+// for every member of a batch in a fixed number of launches.
+
+// Pinned staging of at least `bytes` (allocated before the old one is freed).
+static int hq_grow(fri_ctx* ctx, size_t bytes) {
+    Batch& B = ctx->batch;
+    if (bytes <= B.h_q_cap) return FRI_OK;
+    uint8_t* p = nullptr;
+    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, FRI_ENOMEM, "pinned host allocation failed for the batch's staging");
+    }
+    if (B.h_q) hipHostFree(B.h_q);
+    B.h_q = p;
+    B.h_q_cap = bytes;
+    return FRI_OK;
+}
+
+// The shape's checks and, with q, the composition kernel's constants of it.
+static int fibsq_shape(fri_ctx* ctx, uint32_t log_t, uint32_t log_blowup, uint32_t offset, uint32_t batch,
+                       FibsqParams* q) {
+    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
+    if (log_blowup < 1 || ((uint32_t)1 << log_blowup) > FIBSQ_MAX_B)
+        return fail(ctx, FRI_EINVAL, "log_blowup must be 1..4 (deg CP = T needs n > T)");
+    if (log_t < 2) return fail(ctx, FRI_EINVAL, "trace needs at least 4 rows");
+    if (log_t > FRI_BATCH_MAX_LOG_N || log_t + log_blowup > FRI_BATCH_MAX_LOG_N)
+        return fail(ctx, FRI_EINVAL, "log_t + log_blowup above FRI_BATCH_MAX_LOG_N");
+    const uint32_t L = log_t + log_blowup;
+    if (L > ctx->log_n_max) return fail(ctx, FRI_EINVAL, "log_t + log_blowup out of range for context");
+    if (offset == 0 || offset >= P) return fail(ctx, FRI_EINVAL, "offset must be a nonzero canonical element");
+    const size_t T = (size_t)1 << log_t;
+    const uint32_t Bl = 1u << log_blowup;
+    const uint32_t w = root_of_unity(L), g = root_of_unity(log_t), wB = root_of_unity(log_blowup);
+    const uint32_t offT = pow_std(offset, T);
+    uint32_t zinv[FIBSQ_MAX_B];
+    for (uint32_t j = 0; j < Bl; j++) {
+        const uint32_t z = sub(mul_std(offT, pow_std(wB, j)), 1u);
+        if (z == 0) return fail(ctx, FRI_EINVAL, "offset^T lies in <w_B>: the coset meets the trace domain");
+        zinv[j] = to_mont(inv_std(z));
+    }
+    if (!q) return FRI_OK;
+    *q = FibsqParams{};
+    q->log_n = L;
+    q->B = Bl;
+    q->offset_m = to_mont(offset);
+    q->w_m = to_mont(w);
+    q->winv_m = to_mont(inv_std(w));
+    q->glast_m = to_mont(pow_std(g, T - 1));
+    q->gprev_m = to_mont(pow_std(g, T - 2));
+    for (uint32_t j = 0; j < Bl; j++) q->zinv_m[j] = zinv[j];
+    return FRI_OK;
+}
+
+extern "C" int fri_trace_commit_batch(fri_ctx* ctx, const uint32_t* traces, uint32_t log_t, uint32_t log_blowup,
+                                      uint32_t offset, uint32_t batch, uint8_t* roots32) {
+    if (!ctx || !traces || !roots32) return fail(ctx, FRI_EINVAL, "null argument");
+    int rc = batch_ctx_ok(ctx);
+    if (rc) return rc;
+    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, batch, nullptr))) return rc;
+    const uint32_t L = log_t + log_blowup;
+    const size_t T = (size_t)1 << log_t, n = (size_t)1 << L;
+    for (uint32_t b = 0; b < batch; b++)
+        if (!check_canonical(traces + b * T, T))
+            return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": trace value not canonical (>= p)");
+    FRI_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = batch_quiesce(ctx))) return rc;
+    Batch& B = ctx->batch;
+    if ((rc = batch_tables(ctx, L, offset))) return rc;
+    const size_t tree_stride = 8 * (2 * n);          // levels 0..L: 2n - 1 digests
+    size_t want[BB_N] = {};
+    want[BB_IN] = (size_t)batch * T * 4;
+    want[BB_TCOEF] = (size_t)batch * T * 4;
+    want[BB_SCALED] = L > BATCH_LDS_LDE_MAX_LOG ? (size_t)batch * T * 4 : 0;
+    want[BB_TLDE] = (size_t)batch * n * 4;
+    want[BB_TTREE] = (size_t)batch * tree_stride * 4;
+    want[BB_TROOTS] = (size_t)batch * 32;
+    if ((rc = hq_grow(ctx, (size_t)batch * 32))) return rc;
+    if ((rc = bufs_grow(ctx, B.b, want, 0))) return rc;      // (a failure leaves an older trace batch resident)
+    B.trace_resident = false;
+    hipStream_t s = ctx->stream;
+    uint32_t* in = B.b.words(BB_IN);
+    uint32_t* coef = B.b.words(BB_TCOEF);
+    uint32_t* lde = B.b.words(BB_TLDE);
+    uint32_t* trees = B.b.words(BB_TTREE);
+    uint32_t* roots = B.b.words(BB_TROOTS);
+    FRI_HIP(ctx, hipMemcpyAsync(in, traces, (size_t)batch * T * 4, hipMemcpyHostToDevice, s));
+    batch_intt(ctx, in, T, coef, T, log_t, batch, 1u, s);              // c_j = T^-1 sum_i trace_i w_T^-ij
+    batch_lde(ctx, coef, T, T, lde, n, L, batch, s);                   // on offset * <w_n>
+    launch_trace_trees_batch(lde, n, trees, tree_stride, L, batch, roots, s);
+    FRI_HIP(ctx, hipGetLastError());
+    FRI_HIP(ctx, hipMemcpyAsync(B.h_q, roots, (size_t)batch * 32, hipMemcpyDeviceToHost, s));
+    FRI_HIP(ctx, hipStreamSynchronize(s));
+    for (uint32_t b = 0; b < batch; b++)
+        digest_to_bytes(reinterpret_cast<const uint32_t*>(B.h_q) + 8 * (size_t)b, roots32 + 32 * (size_t)b);
+    B.trace_resident = true;
+    B.trace_count = batch;
+    B.trace_log_t = log_t;
+    B.trace_log_b = log_blowup;
+    B.trace_offset = offset;
+    B.tlde_stride = n;
+    B.ttree_stride = tree_stride;
+    ctx->err.clear();
+    return FRI_OK;
+}
+
+extern "C" int fri_fibsq_composition_commit_batch(fri_ctx* ctx, uint32_t log_t, uint32_t log_blowup, uint32_t offset,
+                                                  uint32_t batch, const uint32_t* a_last, const uint32_t* alphas,
+                                                  const fri_channel_state* chan_in, uint32_t flags,
+                                                  fri_commit_result* out, int* status) {
+    if (!ctx || !a_last || !alphas || !chan_in || !out || !status) return fail(ctx, FRI_EINVAL, "null argument");
+    int rc = batch_ctx_ok(ctx);
+    if (rc) return rc;
+    Batch& B = ctx->batch;
+    if (!B.trace_resident || B.trace_log_t != log_t || B.trace_log_b != log_blowup || B.trace_offset != offset ||
+        B.trace_count != batch)
+        return fail(ctx, FRI_ESTATE, "no resident trace batch with this (log_t, log_blowup, offset, batch)");
+    if (flags & ~FRI_FLAG_NO_GRAPH)
+        return fail(ctx, FRI_EINVAL, "fri_fibsq_composition_commit_batch takes FRI_FLAG_NO_GRAPH only");
+    FibsqParams q;
+    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, batch, &q))) return rc;
+    for (uint32_t b = 0; b < batch; b++)
+        if (a_last[b] >= P || alphas[3 * b] >= P || alphas[3 * b + 1] >= P || alphas[3 * b + 2] >= P)
+            return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": a_last / alphas not canonical");
+    const uint32_t L = log_t + log_blowup;
+    const size_t n = (size_t)1 << L, T = (size_t)1 << log_t;
+    FRI_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = batch_quiesce(ctx))) return rc;
+    size_t want[BB_N] = {};
+    want[BB_CP] = (size_t)batch * n * 4;
+    want[BB_IN] = (size_t)batch * n * 4;
+    want[BB_FIB] = (size_t)batch * sizeof(FibsqMember);
+    if ((rc = hq_grow(ctx, (size_t)batch * sizeof(FibsqMember)))) return rc;
+    if ((rc = bufs_grow(ctx, B.b, want, 0))) return rc;
+    FibsqMember* hm = reinterpret_cast<FibsqMember*>(B.h_q);
+    for (uint32_t b = 0; b < batch; b++) {
+        for (int j = 0; j < 3; j++) hm[b].alpha_m[j] = to_mont(alphas[3 * b + j]);
+        hm[b].a_last = a_last[b];
+    }
+    hipStream_t s = ctx->stream;
+    FibsqMember* dm = static_cast<FibsqMember*>(B.b.dev[BB_FIB]);
+    uint32_t* cp = B.b.words(BB_CP);
+    uint32_t* coef = B.b.words(BB_IN);
+    FRI_HIP(ctx, hipMemcpyAsync(dm, hm, (size_t)batch * sizeof(FibsqMember), hipMemcpyHostToDevice, s));
+    launch_fibsq_cp_batch(B.b.words(BB_TLDE), B.tlde_stride, cp, n, dm, batch, q, s);
+    // coefficients: c_j = n^-1 offset^-j sum_i cp_i w^-ij, all n of them (the
+    // commit's degree scan then sees a composition of degree above T)
+    batch_intt(ctx, cp, n, coef, n, L, batch, inv_std(offset), s);
+    FRI_HIP(ctx, hipGetLastError());
+    return run_batch(ctx, nullptr, coef, n, batch, L, offset, chan_in, flags, nullptr, out, status, true, (uint32_t)T);
+}
+
+extern "C" int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* skip, uint32_t trace_count,
+                                     uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
+                                     size_t paths_stride, size_t* paths_len) {
+    if (!ctx || !indices || !values || !paths || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
+    Batch& B = ctx->batch;
+    if (!B.resident)
+        return fail(ctx, FRI_ESTATE,
+                    "no resident batch: fri_batch_* serve the last fri_commit_batch until the next commit");
+    if (trace_count > 8) return fail(ctx, FRI_EINVAL, "trace_count must be 0..8");
+    const uint32_t L = B.log_n, batch = B.count;
+    if (trace_count && (!B.trace_resident || B.trace_count != batch || B.trace_log_t + B.trace_log_b != L))
+        return fail(ctx, FRI_ESTATE, "no resident trace batch behind this batch (fri_trace_commit_batch)");
+    // who is served, and the record's shape
+    uint32_t max_layers = 0, served = 0;
+    for (uint32_t b = 0; b < batch; b++) {
+        const uint32_t nl = (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers;
+        if (!nl) continue;
+        // (the FRI openings take any index, mod the layer's size, as fri_decommit_query; the trace's do not)
+        if (trace_count && (indices[b] >> L))
+            return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": index out of range");
+        max_layers = std::max(max_layers, nl);
+        served++;
+    }
+    auto fri_path_words = [&](uint32_t nl) { return 16 * ((size_t)nl * L - (size_t)nl * (nl ? nl - 1 : 0) / 2); };
+    const size_t tpath_words = (size_t)trace_count * 8 * L;
+    const size_t val_words = trace_count + 2 * (size_t)max_layers;
+    const size_t rec_words = val_words + tpath_words + fri_path_words(max_layers);
+    if (served && (values_stride < val_words || paths_stride < (tpath_words + fri_path_words(max_layers)) * 4)) {
+        paths_len[0] = (tpath_words + fri_path_words(max_layers)) * 4;
+        return fail(ctx, FRI_EINVAL,
+                    "record strides too small (values: trace_count + 2 per layer words; paths: see paths_len[0])");
+    }
+    for (uint32_t b = 0; b < batch; b++) paths_len[b] = 0;
+    if (!served) return FRI_OK;
+    FRI_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t meta_bytes = (size_t)batch * sizeof(BatchQueryMember), out_bytes = (size_t)batch * rec_words * 4;
+    size_t want[BB_N] = {};
+    want[BB_QMETA] = meta_bytes;
+    want[BB_QOUT] = out_bytes;
+    int rc;
+    if ((rc = hq_grow(ctx, meta_bytes + out_bytes))) return rc;
+    if ((rc = bufs_grow(ctx, B.b, want, 0))) return rc;
+    BatchQueryMember* hm = reinterpret_cast<BatchQueryMember*>(B.h_q);
+    const uint32_t* hout = reinterpret_cast<const uint32_t*>(B.h_q + meta_bytes);
+    for (uint32_t b = 0; b < batch; b++) {
+        hm[b].index = indices[b];
+        hm[b].n_layers = (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers;
+        hm[b].pad = 0;
+    }
+    BatchQuery bq{};
+    bq.layers = B.b.words(BB_LAYERS);
+    bq.trees = B.b.words(BB_TREES);
+    bq.lay_stride = B.lay_stride;
+    bq.tre_stride = B.tre_stride;
+    bq.tlde = B.b.words(BB_TLDE);
+    bq.ttree = B.b.words(BB_TTREE);
+    bq.tlde_stride = B.tlde_stride;
+    bq.ttree_stride = B.ttree_stride;
+    bq.mem = static_cast<const BatchQueryMember*>(B.b.dev[BB_QMETA]);
+    bq.out = B.b.words(BB_QOUT);
+    bq.rec_words = rec_words;
+    bq.trace_stride = trace_stride;
+    bq.log_n = L;
+    bq.trace_count = trace_count;
+    bq.max_layers = max_layers;
+    for (int k = 0; k <= B.lay.rmax + 1; k++) {
+        bq.layer_off[k] = (uint32_t)B.lay.layer_off[k];
+        bq.tree_off[k] = (uint32_t)B.lay.tree_off[k];
+    }
+    hipStream_t s = ctx->stream;
+    FRI_HIP(ctx, hipMemcpyAsync(B.b.dev[BB_QMETA], hm, meta_bytes, hipMemcpyHostToDevice, s));
+    launch_batch_query(bq, batch, s);
+    FRI_HIP(ctx, hipGetLastError());
+    FRI_HIP(ctx, hipMemcpyAsync(B.h_q + meta_bytes, bq.out, out_bytes, hipMemcpyDeviceToHost, s));
+    FRI_HIP(ctx, hipStreamSynchronize(s));
+    for (uint32_t b = 0; b < batch; b++) {
+        const uint32_t nl = hm[b].n_layers;
+        if (!nl) continue;
+        const uint32_t* rec = hout + b * rec_words;
+        uint32_t* v = values + b * values_stride;
+        uint8_t* p = paths + b * paths_stride;
+        memcpy(v, rec, trace_count * 4);
+        memcpy(v + trace_count, rec + trace_count, 2 * (size_t)nl * 4);
+        memcpy(p, rec + val_words, tpath_words * 4);
+        memcpy(p + tpath_words * 4, rec + val_words + tpath_words, fri_path_words(nl) * 4);
+        paths_len[b] = (tpath_words + fri_path_words(nl)) * 4;
+    }
+    ctx->err.clear();
     return FRI_OK;
 }

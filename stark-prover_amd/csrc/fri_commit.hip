@@ -200,6 +200,7 @@ void fri::init_state(fri_ctx* ctx, DevState* h, const fri_channel_state* chan_in
     ctx->h_state = h;
     ctx->res_lane = ctx->cur_lane;
     ctx->batch.resident = false;         // the fri_batch_* read-backs serve a batch only while it is the last commit
+    ctx->batch.trace_resident = false;   // ... and its trace batch goes with it
     ctx->commit_gen++;
     state_reset(h, chan_in, flags, forced_betas);
 }

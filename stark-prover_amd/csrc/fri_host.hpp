@@ -9,8 +9,9 @@
 //   fri_multipoint.hip evaluation and interpolation at arbitrary points, on the tree
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
-//   fri_batch.hip      the batched commit of many small codewords and its
-//                      member-wise read-backs
+//   fri_batch.hip      the batched commit of many small codewords, its
+//                      member-wise read-backs and the batched prover entry
+//                      points (trace commit, composition commit, query round)
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
 //                      which commit the read-backs serve (residency)
 //   fri_readback.hip   read-backs, decommitment and the prover entry points
@@ -119,6 +120,15 @@ enum {
     BB_IN,        // staged input (host coefficients)
     BB_SCALED,    // c_j offset^j, the batched transform's input
     BB_STATES,    // one DevState per member
+    // the batched prover (fri_trace_commit_batch and what follows it)
+    BB_TLDE,      // the members' trace LDEs
+    BB_TTREE,     // ... and their Merkle trees, every level
+    BB_TCOEF,     // trace coefficients (the LDE's input)
+    BB_TROOTS,    // the trace trees' roots, 8 words per member
+    BB_CP,        // composition polynomial on the coset, n words per member
+    BB_FIB,       // one FibsqMember per member
+    BB_QMETA,     // fri_batch_query_round: one BatchQueryMember per member
+    BB_QOUT,      // ... and the members' records
     BB_N
 };
 struct BatchBufs {
@@ -139,6 +149,15 @@ struct Batch {
     uint32_t* pre_lo = nullptr;
     uint32_t* pre_hi = nullptr;
     uint32_t tab_log_n = 0, tab_offset = 0;
+    // The trace batch (fri_trace_commit_batch): resident through the composition
+    // commit that consumes it, until the next trace batch, plain batch or
+    // single commit.
+    bool trace_resident = false;
+    uint32_t trace_count = 0, trace_log_t = 0, trace_log_b = 0, trace_offset = 0;
+    size_t tlde_stride = 0, ttree_stride = 0;    // words
+    // pinned staging of the query rounds and the trace roots (grown on demand)
+    uint8_t* h_q = nullptr;
+    size_t h_q_cap = 0;
 };
 
 struct Team;   // in-process team (defined below)

@@ -304,6 +304,16 @@ void launch_batch_scale(const uint32_t* src, size_t src_stride, uint32_t* dst, s
 void launch_batch_lde_lds(const uint32_t* src, size_t src_stride, size_t d, uint32_t* layers, size_t lay_stride,
                           uint32_t log_n, uint32_t batch, const uint32_t* tw, const uint32_t* lo, const uint32_t* hi,
                           hipStream_t s);
+// The inverse: dst[b * dst_stride + j] = t^j sum_i src[b * src_stride + i] w^-ij, j < 2^log_n, in LDS
+// (log_n <= BATCH_LDS_LDE_MAX_LOG; tw_inv the inverse twiddles, lo / hi the post-scale table of t)
+void launch_batch_intt_lds(const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride, uint32_t log_n,
+                           uint32_t batch, const uint32_t* tw_inv, const uint32_t* lo, const uint32_t* hi,
+                           hipStream_t s);
+// Merkle tree of every member's 2^L values (fri_trace_commit_batch), one 512-thread
+// workgroup each: every level into trees + b * tre_stride (level_offset(L, l),
+// tre_stride in words), the root's 8 words into roots + 8 * b.
+void launch_trace_trees_batch(const uint32_t* lde, size_t lde_stride, uint32_t* trees, size_t tre_stride, uint32_t L,
+                              uint32_t batch, uint32_t* roots, hipStream_t s);
 
 // fri_prover.hip — STARK-101 FibonacciSq composition on the LDE coset.
 constexpr uint32_t FIBSQ_MAX_B = 16;   // blowup <= 2^4
@@ -318,8 +328,37 @@ struct FibsqParams {
     uint32_t zinv_m[FIBSQ_MAX_B];// Montgomery((offset^T w_B^j - 1)^-1), j < B
 };
 void launch_fibsq_cp(const uint32_t* f_lde, uint32_t* out, const FibsqParams& q, hipStream_t s);
+// The batch: trace b's LDE at f_lde + b * f_stride, its CP at out + b * out_stride,
+// its constants in mem[b] (device); q carries the shape (its alpha_m / a_last are not read).
+struct FibsqMember {
+    uint32_t alpha_m[3];         // Montgomery(alpha_0..2)
+    uint32_t a_last;             // canonical a_{T-1}
+};
+void launch_fibsq_cp_batch(const uint32_t* f_lde, size_t f_stride, uint32_t* out, size_t out_stride,
+                           const FibsqMember* mem, uint32_t batch, const FibsqParams& q, hipStream_t s);
 // out[j] = lde[(index + j*stride) mod 2^L], then count paths of L big-endian digests
 void launch_trace_gather(const uint32_t* lde, const uint32_t* tree, uint32_t L, uint64_t index, uint64_t stride,
                          uint32_t count, uint32_t* out, hipStream_t s);
+// One query of every member of a batch, one launch (fri_batch_query_round;
+// k_batch_query has the record's layout).  mem[b].n_layers = 0 leaves member b out.
+struct BatchQueryMember {
+    uint64_t index;
+    uint32_t n_layers, pad;
+};
+struct BatchQuery {
+    const uint32_t* layers;      // the FRI batch (BatchTask's slices and offsets)
+    const uint32_t* trees;
+    size_t lay_stride, tre_stride;
+    const uint32_t* tlde;        // the trace batch (trace_count > 0)
+    const uint32_t* ttree;
+    size_t tlde_stride, ttree_stride;
+    const BatchQueryMember* mem;
+    uint32_t* out;
+    size_t rec_words;
+    uint64_t trace_stride;
+    uint32_t log_n, trace_count, max_layers;
+    uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2];
+};
+void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s);
 
 }  // namespace fri

@@ -1317,6 +1317,126 @@ void launch_batch_lde_lds(const uint32_t* src, size_t src_stride, size_t d, uint
                        log_n, tw, lo, hi);
 }
 
+// Its mirror image, the members' coset interpolation (fri_trace_commit_batch,
+// fri_fibsq_composition_commit_batch): the same DIT with the inverse twiddles,
+// then the post-scale t^j (lo / hi: launch_pow_table with the 1/n factor in
+// hi) on the way out.  dst[b * dst_stride + j] = t^j sum_i src[b * src_stride + i] w^-ij.
+__global__ __launch_bounds__(256) void k_batch_intt_lds(const uint32_t* __restrict__ src, size_t src_stride,
+                                                        uint32_t* __restrict__ dst, size_t dst_stride, uint32_t log_n,
+                                                        const uint32_t* __restrict__ tw, const uint32_t* __restrict__ lo,
+                                                        const uint32_t* __restrict__ hi) {
+    __shared__ uint32_t a[1u << BATCH_LDS_LDE_MAX_LOG];
+    const uint32_t n = 1u << log_n;
+    const uint32_t* in = src + blockIdx.x * src_stride;
+    uint32_t* out = dst + blockIdx.x * dst_stride;
+    for (uint32_t j = threadIdx.x; j < n; j += 256) a[__brev(j) >> (32 - log_n)] = in[j];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s = 0; s < log_n; s++) {
+        const uint32_t half = 1u << s;
+        for (uint32_t idx = threadIdx.x; idx < n / 2; idx += 256) {
+            const uint32_t j = idx & (half - 1), p0 = ((idx >> s) << (s + 1)) + j;
+            const uint32_t u = a[p0], w = mmul(a[p0 + half], tw[half + j]);
+            a[p0] = add(u, w);
+            a[p0 + half] = sub(u, w);
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = threadIdx.x; j < n; j += 256)
+        out[j] = mmul(mmul(a[j], hi[j >> POW_LO_LOG]), lo[j & ((1u << POW_LO_LOG) - 1)]);
+}
+void launch_batch_intt_lds(const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride, uint32_t log_n,
+                           uint32_t batch, const uint32_t* tw_inv, const uint32_t* lo, const uint32_t* hi,
+                           hipStream_t s) {
+    assert(log_n >= 1 && log_n <= BATCH_LDS_LDE_MAX_LOG);
+    hipLaunchKernelGGL(k_batch_intt_lds, dim3(batch), dim3(256), 0, s, src, src_stride, dst, dst_stride, log_n, tw_inv,
+                       lo, hi);
+}
+
+// The members' trace trees (fri_trace_commit_batch): k_commit_batch's layer 0
+// without fold, coefficients or channel.  Member blockIdx.x hashes its 2^L LDE
+// values and stores every level in its tree slice (level_offset(L, l), what
+// k_trace_gather reads) and its root in roots[8 * member ..].  L <= TAIL_LOG:
+// one level loop from the leaves; above, tiles of 2^TAIL_LOG leaves climb nine
+// levels in LDS and the level loop runs over the tile roots.  As in
+// k_commit_batch every word is produced and consumed by this workgroup.
+__global__ __launch_bounds__(512) void k_trace_trees_batch(const uint32_t* __restrict__ lde, size_t lde_stride,
+                                                           uint32_t* __restrict__ trees, size_t tre_stride, uint32_t L,
+                                                           uint32_t* __restrict__ roots) {
+    constexpr uint32_t NMAX = 1u << TAIL_LOG;
+    __shared__ uint4 lds[2 * NMAX + NMAX];
+    __shared__ SchedLds sl;
+    sched_init(&sl);
+    uint32_t ord = 0;
+    const uint32_t tid = threadIdx.x;
+    const size_t mb = blockIdx.x;
+    const uint32_t* values = lde + mb * lde_stride;
+    uint32_t* tr = trees + mb * tre_stride;
+    if (tid >= 384 && tid < 448) kcache_touch_sha_tables();
+    const shaq::Role R = shaq::role_of(tid);
+    const uint32_t N = 1u << L;
+    LayerTask t{};
+    t.L = L;
+    uint4* A = lds;
+    uint4* B = lds + 2 * NMAX;
+    uint32_t N2 = N, lvl0 = 0;
+    if (L > TAIL_LOG) {
+        const uint32_t tiles = N >> TAIL_LOG;
+#pragma unroll 1
+        for (uint32_t tile = 0; tile < tiles; tile++) {
+            A = lds;
+            B = lds + 2 * NMAX;
+            const uint32_t i = (tile << TAIL_LOG) + tid;
+            Dg d;
+            cleaf(values[i], d);
+            dg_store(tr + 8 * (size_t)i, d);
+            dg_lds_store(A + 2 * tid, d);
+            lds_barrier();
+            uint32_t cnt = NMAX;
+#pragma unroll 1
+            for (uint32_t j = 1; j <= TAIL_LOG; j++) {
+                cnt >>= 1;
+                level_step(t, false, 0, A, B, tr + 8 * (level_offset(L, j) + ((size_t)tile << (TAIL_LOG - j))), cnt, R,
+                           &sl, ord++);
+                lds_barrier();
+                uint4* tmp = A; A = B; B = tmp;
+            }
+        }
+        __syncthreads();                                 // the tile roots, written by this workgroup
+        N2 = tiles;
+        lvl0 = TAIL_LOG;
+        A = lds;
+        B = lds + 2 * NMAX;
+        const uint32_t* in = tr + 8 * level_offset(L, TAIL_LOG);
+        for (uint32_t i = tid; i < N2; i += blockDim.x) {
+            Dg d;
+            dg_load(in + 8 * i, d);
+            dg_lds_store(A + 2 * i, d);
+        }
+    } else {
+        leaf_loop(N, tr, A, [&](uint32_t j, bool) { return values[j]; });
+    }
+    lds_barrier();
+    uint32_t cnt = N2;
+#pragma unroll 1
+    for (uint32_t it = 0; it < L - lvl0; it++) {
+        cnt >>= 1;
+        level_step(t, false, it, A, B, tr + 8 * level_offset(L, lvl0 + 1 + it), cnt, R, &sl, ord++);
+        lds_barrier();
+        uint4* tmp = A; A = B; B = tmp;
+    }
+    if (tid == 0) {
+        Dg root;
+        dg_lds_load(A, root);
+        dg_store(roots + 8 * mb, root);
+    }
+}
+void launch_trace_trees_batch(const uint32_t* lde, size_t lde_stride, uint32_t* trees, size_t tre_stride, uint32_t L,
+                              uint32_t batch, uint32_t* roots, hipStream_t s) {
+    assert(L >= 1 && L <= BATCH_MAX_LOG);
+    hipLaunchKernelGGL(k_trace_trees_batch, dim3(batch), dim3(512), 0, s, lde, lde_stride, trees, tre_stride, L, roots);
+}
+
 // ------------------------------------------------------------ launcher ----
 // Layer schedule of launch_layer (D = L - l: log2 of the nodes still to climb):
 //   L <= 9 : one k_tree_top from the leaves (standalone trees only; a commit

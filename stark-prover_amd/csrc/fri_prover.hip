@@ -21,8 +21,11 @@ namespace fri {
 
 constexpr uint32_t CP_K = 16;     // points per lane
 
-__global__ __launch_bounds__(256) void k_fibsq_cp(const uint32_t* __restrict__ f, uint32_t* __restrict__ out,
-                                                  FibsqParams q) {
+// One lane's CP_K points of one trace: f and out are that trace's n-word
+// buffers, alpha_m / a_last its constants (the rest of q is the shape's).
+__device__ __forceinline__ void fibsq_cp_lane(const uint32_t* __restrict__ f, uint32_t* __restrict__ out,
+                                              const FibsqParams& q, uint32_t alpha0_m, uint32_t alpha1_m,
+                                              uint32_t alpha2_m, uint32_t a_last) {
     const size_t n = (size_t)1 << q.log_n;
     const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * CP_K;
     if (i0 >= n) return;
@@ -53,19 +56,43 @@ __global__ __launch_bounds__(256) void k_fibsq_cp(const uint32_t* __restrict__ f
         const size_t i = (i0 + k) & mask;
         const uint32_t fi = f[i], f1 = f[(i + q.B) & mask], f2 = f[(i + 2 * q.B) & mask];
         const uint32_t p0 = mmul(sub(fi, 1u), mmul(dinv, xb[k]));        // (f-1)/(x-1)
-        const uint32_t p1 = mmul(sub(fi, q.a_last), mmul(dinv, xa[k]));  // (f-A)/(x-g^{T-1})
+        const uint32_t p1 = mmul(sub(fi, a_last), mmul(dinv, xa[k]));  // (f-A)/(x-g^{T-1})
         const uint32_t sq = add(mmul(f1, to_mont(f1)), mmul(fi, to_mont(fi)));
         const uint32_t num2 = sub(f2, sq);
         const uint32_t zf = mmul(mmul(sub(x, q.gprev_m), xb[k]), q.zinv_m[i & (q.B - 1)]);
         const uint32_t p2 = mmul(num2, zf);
-        out[i] = add(add(mmul(p0, q.alpha_m[0]), mmul(p1, q.alpha_m[1])), mmul(p2, q.alpha_m[2]));
+        out[i] = add(add(mmul(p0, alpha0_m), mmul(p1, alpha1_m)), mmul(p2, alpha2_m));
         x = mmul(x, q.winv_m);
     }
+}
+
+__global__ __launch_bounds__(256) void k_fibsq_cp(const uint32_t* __restrict__ f, uint32_t* __restrict__ out,
+                                                  FibsqParams q) {
+    fibsq_cp_lane(f, out, q, q.alpha_m[0], q.alpha_m[1], q.alpha_m[2], q.a_last);
 }
 
 void launch_fibsq_cp(const uint32_t* f_lde, uint32_t* out, const FibsqParams& q, hipStream_t s) {
     const size_t lanes = (((size_t)1 << q.log_n) + CP_K - 1) / CP_K;
     hipLaunchKernelGGL(k_fibsq_cp, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, f_lde, out, q);
+}
+
+// The batch (fri_fibsq_composition_commit_batch): trace blockIdx.y of one
+// shape, its LDE and output at b * stride, its alphas and a_last in mem[b].
+// The n = 8 wrap of fibsq_cp_lane stays inside the member's n words: the
+// index is masked before the member's base is added.
+__global__ __launch_bounds__(256) void k_fibsq_cp_batch(const uint32_t* __restrict__ f, size_t f_stride,
+                                                        uint32_t* __restrict__ out, size_t out_stride,
+                                                        const FibsqMember* __restrict__ mem, FibsqParams q) {
+    const size_t b = blockIdx.y;
+    const FibsqMember m = mem[b];
+    fibsq_cp_lane(f + b * f_stride, out + b * out_stride, q, m.alpha_m[0], m.alpha_m[1], m.alpha_m[2], m.a_last);
+}
+
+void launch_fibsq_cp_batch(const uint32_t* f_lde, size_t f_stride, uint32_t* out, size_t out_stride,
+                           const FibsqMember* mem, uint32_t batch, const FibsqParams& q, hipStream_t s) {
+    const size_t lanes = (((size_t)1 << q.log_n) + CP_K - 1) / CP_K;
+    hipLaunchKernelGGL(k_fibsq_cp_batch, dim3((unsigned)((lanes + 255) / 256), batch), dim3(256), 0, s, f_lde, f_stride,
+                       out, out_stride, mem, q);
 }
 
 // Trace-tree decommitment (STARK-101 decommit_on_query): values at
@@ -87,6 +114,61 @@ __global__ void k_trace_gather(const uint32_t* __restrict__ lde, const uint32_t*
 void launch_trace_gather(const uint32_t* lde, const uint32_t* tree, uint32_t L, uint64_t index, uint64_t stride,
                          uint32_t count, uint32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_trace_gather, dim3(count), dim3(64), 0, s, lde, tree, L, index, stride, out, count);
+}
+
+// One query of every member of a batch (fri_batch_query_round): block
+// (x, member), lane l = tree level l.  x < trace_count opens the member's trace
+// LDE at index + x * trace_stride (k_trace_gather's value and path); above,
+// x - trace_count is a FRI layer k of the member: the values at idx = index mod
+// m_k and its sibling and their two paths (k_decommit_gather).  A member's
+// record is rec_words words at out + member * rec_words:
+//   [trace values][2 * max_layers FRI values][trace paths, 8 L words each]
+//   [FRI paths, layer k's two at 16 (k L - k (k - 1) / 2)]
+// of which a member with fewer layers fills a prefix of each part.  A member
+// with n_layers = 0 in mem (skipped, or its commit failed) writes nothing.
+__global__ __launch_bounds__(64) void k_batch_query(BatchQuery q) {
+    const uint32_t x = blockIdx.x, l = threadIdx.x;
+    const size_t b = blockIdx.y;
+    const BatchQueryMember m = q.mem[b];
+    if (m.n_layers == 0) return;
+    const uint32_t L = q.log_n, tc = q.trace_count;
+    uint32_t* rec = q.out + b * q.rec_words;
+    uint32_t* tpaths = rec + tc + 2 * q.max_layers;
+    if (x < tc) {
+        const uint64_t leaf = (m.index + x * q.trace_stride) & (((uint64_t)1 << L) - 1);
+        if (l == 0) rec[x] = q.tlde[b * q.tlde_stride + leaf];
+        if (l >= L) return;
+        const uint32_t* d = q.ttree + b * q.ttree_stride + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
+        uint32_t* o = tpaths + (size_t)x * 8 * L + 8 * l;
+#pragma unroll
+        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+        return;
+    }
+    const uint32_t k = x - tc;
+    if (k >= m.n_layers) return;
+    const uint32_t Lk = L - k;
+    const uint64_t mk = (uint64_t)1 << Lk;
+    const uint64_t idx = m.index % mk, sib = (idx + mk / 2) % mk;
+    const uint32_t* lay = q.layers + b * q.lay_stride + q.layer_off[k];
+    if (l == 0) {
+        rec[tc + 2 * k] = lay[idx];
+        rec[tc + 2 * k + 1] = lay[sib];
+    }
+    if (l >= Lk) return;
+    const uint32_t* tr = q.trees + b * q.tre_stride + q.tree_off[k];
+    uint32_t* paths = tpaths + (size_t)tc * 8 * L + 16 * ((size_t)k * L - (size_t)k * (k - 1) / 2);
+#pragma unroll
+    for (int which = 0; which < 2; which++) {
+        const uint64_t leaf = which ? sib : idx;
+        const uint32_t* d = tr + 8 * (level_offset(Lk, l) + ((leaf >> l) ^ 1u));
+        uint32_t* o = paths + (size_t)which * 8 * Lk + 8 * l;
+#pragma unroll
+        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+    }
+}
+
+void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_batch_query, dim3(q.trace_count + q.max_layers, batch), dim3(64), 0, s, q);
 }
 
 }  // namespace fri

@@ -441,17 +441,20 @@ std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>& polys, uint32_t 
                                 static_cast<uint32_t>(offset.value()), cin.data(), 0, nullptr, res.data(), status.data()),
                "fri_commit_batch");
     std::vector<FRIProof> out;
-    for (size_t b = 0; b < B; b++) {
-        FRIProof proof = FRIProof::mirror(res[b], log_n, gpu, channels[b], gen);
-        proof.member_ = static_cast<int>(b);
-        for (MerkleTree& t : proof.fri_merkles) {
-            t.member_ = proof.member_;
-            t.log_n_ = log_n;
-            t.n_layers_ = res[b].n_layers;
-        }
-        out.push_back(std::move(proof));
-    }
+    for (size_t b = 0; b < B; b++) out.push_back(FRIProof::mirror_member(res[b], log_n, gpu, channels[b], gen, b));
     return out;
+}
+
+FRIProof FRIProof::mirror_member(const fri_commit_result& res, uint32_t log_n, const std::shared_ptr<Gpu>& gpu,
+                                 FriChannel& channel, uint64_t gen, size_t member) {
+    FRIProof proof = mirror(res, log_n, gpu, channel, gen);
+    proof.member_ = static_cast<int>(member);
+    for (MerkleTree& t : proof.fri_merkles) {
+        t.member_ = proof.member_;
+        t.log_n_ = log_n;
+        t.n_layers_ = res.n_layers;
+    }
+    return proof;
 }
 
 FRIProof FRIProof::mirror(const fri_commit_result& res, uint32_t log_n, const std::shared_ptr<Gpu>& gpu,
@@ -556,6 +559,75 @@ void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, F
     for (size_t q = 0; q < num_queries; q++) {
         const uint64_t idx = channel.receive_random_int(0, max_index, true);
         decommit_fri_layers(idx, proof, channel);
+    }
+}
+
+namespace {
+// One fri_batch_query_round on `gpu` for members of `n_layers[b]` layers, then
+// every channel absorbs its record: trace_count (value, path) pairs, then the
+// layers' openings as decommit_query sends them.
+void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_layers,
+                 const std::vector<uint64_t>& indices, uint32_t trace_count, uint64_t trace_stride,
+                 std::vector<FriChannel>& channels) {
+    const size_t B = channels.size(), tpath = 32 * size_t{log_n};
+    uint64_t generation = 0;
+    uint32_t members = 0, resident_log_n = 0;
+    gpu.check(fri_batch_info(gpu.ctx(), &generation, &members, &resident_log_n), "fri_batch_info");
+    if (members != B) throw Panic("fri_batch_query_round: one index per member of the resident batch");
+    size_t max_layers = 0;
+    for (size_t nl : n_layers) max_layers = std::max(max_layers, nl);
+    size_t fri_bytes = 0;
+    for (size_t k = 0; k < max_layers; k++) fri_bytes += 2 * 32 * (log_n - k);
+    const size_t vstride = trace_count + 2 * max_layers, pstride = std::max<size_t>(trace_count * tpath + fri_bytes, 1);
+    std::vector<uint32_t> values(B * vstride);
+    std::vector<uint8_t> paths(B * pstride);
+    std::vector<size_t> got(B, 0);
+    gpu.check(fri_batch_query_round(gpu.ctx(), indices.data(), nullptr, trace_count, trace_stride, values.data(), vstride,
+                                    paths.data(), pstride, got.data()),
+              "fri_batch_query_round");
+    for (size_t b = 0; b < B; b++) {
+        const uint32_t* v = values.data() + b * vstride;
+        const uint8_t* p = paths.data() + b * pstride;
+        size_t want = trace_count * tpath;
+        for (size_t k = 0; k < n_layers[b]; k++) want += 2 * 32 * (log_n - k);
+        if (got[b] != want) throw Panic("fri_batch_query_round: member " + std::to_string(b) + " was not served");
+        FriChannel& ch = channels[b];
+        for (size_t j = 0; j < trace_count; j++) {
+            ch.send(FE(v[j]).to_bytes());
+            ch.send(p + j * tpath, tpath);
+        }
+        size_t off = trace_count * tpath;
+        for (size_t k = 0; k < n_layers[b]; k++) {
+            const size_t depth = log_n - k, pb = 32 * depth;
+            auto val = FE(v[trace_count + 2 * k]).to_bytes(), sval = FE(v[trace_count + 2 * k + 1]).to_bytes();
+            if (depth == 0) ch.send(val);            // fri_commit.rs:147-149: length == 1 sends it first
+            ch.send(val);
+            ch.send(p + off, pb);
+            ch.send(sval);
+            ch.send(p + off + pb, pb);
+            off += 2 * pb;
+        }
+    }
+}
+}  // namespace
+
+void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
+                        std::vector<FriChannel>& channels) {
+    if (channels.size() != proofs.size()) throw Panic("decommit_fri_batch: one channel per proof");
+    if (proofs.empty()) return;
+    const FRIProof& p0 = proofs[0];
+    std::vector<size_t> n_layers;
+    for (size_t b = 0; b < proofs.size(); b++) {
+        const FRIProof& p = proofs[b];
+        if (p.gpu_ != p0.gpu_ || p.gen_ != p0.gen_ || p.log_n != p0.log_n || p.member_ != static_cast<int>(b))
+            throw Panic("decommit_fri_batch: the proofs are not the members of one batch, in member order");
+        n_layers.push_back(p.n_layers());
+    }
+    p0.require_resident();
+    std::vector<uint64_t> idx(proofs.size());
+    for (size_t q = 0; q < num_queries; q++) {
+        for (size_t b = 0; b < proofs.size(); b++) idx[b] = channels[b].receive_random_int(0, max_index, true);
+        query_round(*p0.gpu_, p0.log_n, n_layers, idx, 0, 0, channels);
     }
 }
 
@@ -764,6 +836,85 @@ StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_qu
         decommit_fri_layers(idx, sp.fri, channel);
     }
     return sp;
+}
+
+namespace {
+// The one-device Gpu of the batched calls beside a default team: per thread,
+// on the team's first device (FRI_DEVICES' first entry, else device 0).
+std::shared_ptr<Gpu> beside_team(uint32_t log_n) {
+    static thread_local std::shared_ptr<Gpu> g;
+    const uint32_t want = log_n < 12 ? 12 : log_n;
+    if (!g || g->log_n_max() < want) {
+        const char* e = std::getenv("FRI_DEVICES");
+        g = std::make_shared<Gpu>(e && *e ? std::atoi(e) : 0, want);
+    }
+    return g;
+}
+}  // namespace
+
+std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
+                                          size_t num_queries, std::vector<FriChannel>& channels, FE offset,
+                                          std::shared_ptr<Gpu> gpu) {
+    if (channels.size() != a1.size()) throw Panic("prove_fibsq_batch: one channel per proof");
+    if (a1.empty()) return {};
+    const uint32_t L = log_t + log_blowup;
+    const uint64_t Bl = uint64_t{1} << log_blowup, n = uint64_t{1} << L;
+    const size_t B = a1.size(), T = size_t{1} << log_t;
+    if (!gpu) {
+        gpu = Gpu::thread_default(L);
+        if (gpu->n_ranks() > 1) gpu = beside_team(L);        // batches run on one device
+    }
+    if (gpu->n_ranks() > 1) throw Panic("prove_fibsq_batch: batches run on a one-device Gpu");
+    if (L > gpu->log_n_max()) throw Panic("prove_fibsq_batch: LDE 2^" + std::to_string(L) + " exceeds the context");
+    const uint32_t off = static_cast<uint32_t>(offset.value());
+    std::vector<uint32_t> traces(B * T), a_last(B), alphas(3 * B);
+    for (size_t b = 0; b < B; b++) {
+        gpu->check(fri_fibsq_trace(static_cast<uint32_t>(a1[b].value()), log_t, traces.data() + b * T), "fri_fibsq_trace");
+        a_last[b] = traces[b * T + T - 1];
+    }
+    std::vector<uint8_t> roots(32 * B);
+    gpu->check(fri_trace_commit_batch(gpu->ctx(), traces.data(), log_t, log_blowup, off, static_cast<uint32_t>(B),
+                                      roots.data()),
+               "fri_trace_commit_batch");
+    std::vector<StarkProof> out(B);
+    std::vector<fri_channel_state> cin(B);
+    for (size_t b = 0; b < B; b++) {
+        StarkProof& sp = out[b];
+        sp.log_t = log_t;
+        sp.log_blowup = log_blowup;
+        sp.a_last = FE(a_last[b]);
+        std::memcpy(sp.trace_root.data(), roots.data() + 32 * b, 32);
+        const std::string root_hex = sha::hex(sp.trace_root.data(), 32);
+        channels[b].send(reinterpret_cast<const uint8_t*>(root_hex.data()), root_hex.size());
+        for (size_t j = 0; j < 3; j++) {
+            sp.alphas[j] = channels[b].receive_random_field_element();
+            alphas[3 * b + j] = static_cast<uint32_t>(sp.alphas[j].value());
+        }
+        auto st = sha::from_hex(channels[b].state);
+        std::memcpy(cin[b].digest, st.data(), 32);
+        cin[b].has_state = 1;
+    }
+    std::vector<fri_commit_result> res(B);
+    std::vector<int> status(B, 0);
+    const uint64_t gen = gpu->bump();
+    gpu->check(fri_fibsq_composition_commit_batch(gpu->ctx(), log_t, log_blowup, off, static_cast<uint32_t>(B),
+                                                  a_last.data(), alphas.data(), cin.data(), 0, res.data(),
+                                                  status.data()),
+               "fri_fibsq_composition_commit_batch");
+    std::vector<size_t> n_layers(B);
+    for (size_t b = 0; b < B; b++) {
+        out[b].fri = FRIProof::mirror_member(res[b], L, gpu, channels[b], gen, b);
+        n_layers[b] = res[b].n_layers;
+    }
+    std::vector<uint64_t> idx(B);
+    for (size_t q = 0; q < num_queries; q++) {
+        for (size_t b = 0; b < B; b++) {
+            idx[b] = channels[b].receive_random_int(0, n - 2 * Bl - 1, true);
+            out[b].queries.push_back(idx[b]);
+        }
+        query_round(*gpu, L, n_layers, idx, 3, Bl, channels);
+    }
+    return out;
 }
 
 FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alphas, FE a_last, uint32_t log_t) {

@@ -505,13 +505,19 @@ class FRIProof {
     friend std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                   const std::shared_ptr<Gpu>&);
     friend void decommit_fri_layers(size_t, const FRIProof&, FriChannel&);
+    friend void decommit_fri_batch(size_t, size_t, const std::vector<FRIProof>&, std::vector<FriChannel>&);
     friend StarkProof prove_fibsq(FE, uint32_t, uint32_t, size_t, FriChannel&, FE, std::shared_ptr<Gpu>);
+    friend std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>&, uint32_t, uint32_t, size_t,
+                                                     std::vector<FriChannel>&, FE, std::shared_ptr<Gpu>);
     // The proof of a device commit: appends the messages the device sent
     // (root hex per layer, beta per round, final value) to `channel` and
     // takes over its state (fri_commit.rs:84-114).
     // gen: the Gpu generation of that commit (default: the current one).
     static FRIProof mirror(const fri_commit_result& res, uint32_t log_n, const std::shared_ptr<Gpu>& gpu,
                            FriChannel& channel, uint64_t gen = 0);
+    // ... of member `member` of a batch: the proof and its trees remember it.
+    static FRIProof mirror_member(const fri_commit_result& res, uint32_t log_n, const std::shared_ptr<Gpu>& gpu,
+                                  FriChannel& channel, uint64_t gen, size_t member);
     std::shared_ptr<Gpu> gpu_;
     uint64_t gen_ = 0;
     int member_ = -1;
@@ -549,6 +555,12 @@ std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>& polys, uint32_t 
 // fri_commit.rs:137-179 over the device-resident layers and trees.
 void decommit_fri_layers(size_t index, const FRIProof& proof, FriChannel& channel);
 void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel);
+// decommit_fri for every member of one batch (`proofs` as fri_commit_batch or
+// prove_fibsq_batch returned them, in member order): per round every channel
+// draws its index, ONE fri_batch_query_round opens them all, and every channel
+// absorbs its openings as decommit_fri_layers sends them.
+void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
+                        std::vector<FriChannel>& channels);
 // The reference's own signature, decommit_fri(num_queries, max_index,
 // &fri_layers, &fri_merkles, &mut channel) (fri_commit.rs:168-174): the
 // commit is found through the device-backed trees (their Gpu and
@@ -590,6 +602,17 @@ struct StarkProof {
 std::vector<FE> fibsq_trace(FE a1, uint32_t log_t);
 StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_queries, FriChannel& channel,
                        FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr);
+// prove_fibsq for many proofs of one shape, proof i with its own a1[i] and
+// channels[i], in a fixed number of device calls: one fri_trace_commit_batch,
+// one fri_fibsq_composition_commit_batch and one fri_batch_query_round per
+// query round (log_t + log_blowup <= FRI_BATCH_MAX_LOG_N, a one-device Gpu;
+// without one, a one-device Gpu beside a default team).  channels[i] ends
+// byte for byte as prove_fibsq(a1[i], ..., channels[i]) leaves it.  A member
+// whose trace violates the constraints panics after the device calls, naming
+// the member.  An empty a1 returns an empty vector.
+std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
+                                          size_t num_queries, std::vector<FriChannel>& channels,
+                                          FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr);
 // CP(x) from f(x), f(gx), f(g^2 x): what layer 0 must hold at a query.
 FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alphas, FE a_last, uint32_t log_t);
 // Verifier of prove_fibsq's transcript: replays the channel, checks the

@@ -195,6 +195,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_batch_commit_degrees": (i32, [vp, u32, ctypes.POINTER(ctypes.c_int32), sz, ctypes.POINTER(u32)]),
         "fri_batch_decommit_query": (i32, [vp, u32, ctypes.c_uint64, pu32, sz, ctypes.c_char_p, sz,
                                            ctypes.POINTER(sz)]),
+        "fri_trace_commit_batch": (i32, [vp, pu32, u32, u32, u32, u32, ctypes.c_char_p]),
+        "fri_fibsq_composition_commit_batch": (i32, [vp, u32, u32, u32, u32, pu32, pu32, ctypes.POINTER(ChannelState),
+                                                     u32, ctypes.POINTER(CommitResult), ctypes.POINTER(i32)]),
+        "fri_batch_query_round": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8), u32,
+                                        ctypes.c_uint64, pu32, sz, ctypes.POINTER(ctypes.c_uint8), sz,
+                                        ctypes.POINTER(sz)]),
         "fri_debug_transport_log": (i32, [vp, ctypes.POINTER(TransportOp), sz, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
@@ -602,6 +608,93 @@ class Context:
             out.append((int(vals[2 * k]), int(vals[2 * k + 1]), buf.raw[off:off + pl], buf.raw[off + pl:off + 2 * pl]))
             off += 2 * pl
         return out
+
+    # ---- batched prover ----------------------------------------------------
+    def trace_commit_batch(self, traces, log_blowup: int, offset: int = GENERATOR) -> List[bytes]:
+        """fri_trace_commit_batch: the LDE Merkle root of every row of
+        ``traces`` (batch x 2^log_t canonical values); LDEs and trees stay
+        resident for fibsq_composition_commit_batch and batch_query_round."""
+        tr = np.ascontiguousarray(np.stack([_u32(t).reshape(-1) for t in traces])) if len(traces) else \
+            np.zeros((0, 0), dtype=np.uint32)
+        batch, T = tr.shape
+        if batch == 0:
+            return []
+        log_t = T.bit_length() - 1
+        if T != 1 << log_t:
+            raise FriError(FRI_EINVAL, "trace length must be a power of two")
+        roots = ctypes.create_string_buffer(32 * batch)
+        self._check(self.lib.fri_trace_commit_batch(self.h, _ptr(tr), log_t, log_blowup, offset, batch, roots))
+        return [roots.raw[32 * b: 32 * b + 32] for b in range(batch)]
+
+    def fibsq_composition_commit_batch(self, log_t: int, log_blowup: int, a_lasts, alphas, offset: int = GENERATOR,
+                                       channel_states=None, graph: bool = True):
+        """fri_fibsq_composition_commit_batch on the resident trace batch:
+        one CommitResult per member.  alphas: three per member;
+        channel_states: per member 32 digest bytes or None.  A member that
+        failed raises FriError after the call; ``self.batch_status`` keeps
+        every member's code and ``self.batch_results`` every result."""
+        al_last = _u32(a_lasts).reshape(-1)
+        batch = al_last.size
+        if not (isinstance(alphas, np.ndarray) and alphas.dtype == np.uint32):
+            alphas = np.asarray(alphas, dtype=np.uint64)
+        al = _u32(alphas.reshape(-1))
+        if al.size != 3 * batch:
+            raise FriError(FRI_EINVAL, "three alphas per member")
+        if channel_states is None:
+            channel_states = [None] * batch
+        if len(channel_states) != batch:
+            raise FriError(FRI_EINVAL, "one channel state per member")
+        chs = (ChannelState * max(batch, 1))()
+        for b, st in enumerate(channel_states):
+            if st:
+                ctypes.memmove(chs[b].digest, st, 32)
+                chs[b].has_state = 1
+        res = (CommitResult * max(batch, 1))()
+        status = (ctypes.c_int * max(batch, 1))()
+        rc = self.lib.fri_fibsq_composition_commit_batch(self.h, log_t, log_blowup, offset, batch, _ptr(al_last),
+                                                         _ptr(al), chs, 0 if graph else FLAG_NO_GRAPH, res, status)
+        self.batch_status = [int(x) for x in status][:batch]
+        self.batch_results = list(res)[:batch]
+        self._check(rc)
+        return self.batch_results
+
+    def batch_query_round(self, indices, skip=None, trace_count: int = 0, trace_stride: int = 0, values=None,
+                          paths=None):
+        """fri_batch_query_round: one query of every member of the resident
+        batch in one launch.  Returns (values, paths, paths_len): uint32
+        (batch, values_stride) and uint8 (batch, paths_stride) arrays (the
+        caller's, when given) and the bytes written per member, 0 for a
+        member that was skipped or whose commit failed.  batch_round_records
+        takes a member's record apart."""
+        _, members, log_n = self.batch_info()
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64))
+        if members and idx.size != members:
+            raise FriError(FRI_EINVAL, "one index per member of the resident batch")
+        batch = idx.size                          # (no resident batch: the library refuses before it reads any)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(np.asarray(skip, dtype=np.uint8))
+            if sk.size != batch:
+                raise FriError(FRI_EINVAL, "one skip flag per member")
+        nl = log_n + 1
+        if values is None:
+            values = np.zeros((batch, trace_count + 2 * nl), dtype=np.uint32)
+        if paths is None:
+            paths = np.zeros((batch, max(32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(nl)), 1)),
+                             dtype=np.uint8)
+        if values.dtype != np.uint32 or paths.dtype != np.uint8 or values.ndim != 2 or paths.ndim != 2 or \
+                values.shape[0] != batch or paths.shape[0] != batch or not values.flags["C_CONTIGUOUS"] or \
+                not paths.flags["C_CONTIGUOUS"]:
+            raise FriError(FRI_EINVAL, "values: C-contiguous uint32 (batch, stride); paths: uint8 (batch, stride)")
+        ln = (ctypes.c_size_t * max(batch, 1))()
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        rc = self.lib.fri_batch_query_round(self.h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                            sk.ctypes.data_as(u8p) if sk is not None else None, trace_count,
+                                            trace_stride, _ptr(values), values.shape[1], paths.ctypes.data_as(u8p),
+                                            paths.shape[1], ln)
+        self.round_needed = int(ln[0]) if rc == FRI_EINVAL else 0     # (too-small strides: the needed paths stride)
+        self._check(rc)
+        return values, paths, [int(x) for x in ln][:batch]
 
     def commit_info(self):
         """(generation, log_n, n_layers) of the resident commit (fri_commit_info)."""
@@ -1579,6 +1672,95 @@ def fri_commit_batch(polys: Sequence[Sequence[int]], log_n: int, channels: Seque
         proof.member = b
         out.append(proof)
     return out
+
+
+def batch_round_records(values: np.ndarray, paths: np.ndarray, paths_len: int, trace_count: int, n_layers: int,
+                        log_n: int):
+    """One member's record of Context.batch_query_round (its rows of values
+    and paths, the bytes written) taken apart: ([(trace value, path)] *
+    trace_count, decommit_query's tuples for the member's n_layers)."""
+    tl = 32 * log_n
+    if paths_len != trace_count * tl + sum(64 * (log_n - k) for k in range(n_layers)):
+        raise FriError(FRI_ESTATE, "the record does not hold this many layers (a skipped or failed member?)")
+    raw = paths[:paths_len].tobytes()
+    trace = [(int(values[j]), raw[j * tl:(j + 1) * tl]) for j in range(trace_count)]
+    off, openings = trace_count * tl, []
+    for k in range(n_layers):
+        pl = 32 * (log_n - k)
+        openings.append((int(values[trace_count + 2 * k]), int(values[trace_count + 2 * k + 1]), raw[off:off + pl],
+                         raw[off + pl:off + 2 * pl]))
+        off += 2 * pl
+    return trace, openings
+
+
+def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIProof"],
+                       channels: Sequence[Channel]) -> None:
+    """decommit_fri (fri_commit.rs:168-179) for every member of one batch
+    (``proofs`` as fri_commit_batch or prove_fibsq_batch returned them, in
+    member order): per round every channel draws its index, ONE
+    fri_batch_query_round opens them all, and every channel absorbs its
+    openings as decommit_fri_layers sends them."""
+    if len(proofs) != len(channels):
+        raise FriError(FRI_EINVAL, "one channel per proof")
+    if len(proofs) == 0:
+        return
+    ctx, gen, log_n = proofs[0].ctx.ctx, proofs[0].generation, proofs[0].log_n
+    if any(not isinstance(p.ctx, BatchMember) or p.ctx.ctx is not ctx or p.generation != gen or p.member != b
+           for b, p in enumerate(proofs)):
+        raise FriError(FRI_EINVAL, "proofs are not the members of one batch, in member order")
+    g, members, ln = ctx.batch_info()
+    if g != gen or members != len(proofs) or ln != log_n:
+        raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
+    for _ in range(num_queries):
+        idx = [ch.receive_random_int(0, max_index, True) for ch in channels]
+        values, paths, lens = ctx.batch_query_round(idx)
+        for b, (p, ch) in enumerate(zip(proofs, channels)):
+            _send_openings(batch_round_records(values[b], paths[b], lens[b], 0, p.n_layers, log_n)[1], ch)
+
+
+def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queries: int, channels: Sequence[Channel],
+                      offset: int = GENERATOR, ctx: Optional[Context] = None) -> List[StarkProof]:
+    """prove_fibsq for many proofs of one shape, each with its own a1 and
+    channel, in a fixed number of device calls: one fri_trace_commit_batch,
+    one fri_fibsq_composition_commit_batch and one fri_batch_query_round per
+    query round.  Member i's transcript (``channels[i].proof``) and state are
+    what prove_fibsq(a1s[i], ...) into channels[i] gives.  A member whose
+    trace violates the constraints raises FriError after the whole batch ran
+    (the message names the member)."""
+    if len(a1s) != len(channels):
+        raise FriError(FRI_EINVAL, "one channel per proof")
+    if len(a1s) == 0:
+        return []
+    L = log_t + log_blowup
+    B, n = 1 << log_blowup, 1 << L
+    ctx = _beside_team(ctx or _default_ctx(L), L, _BATCH_CTX)     # batches run on one device
+    traces = np.stack([fibsq_trace(a1, 1 << log_t) for a1 in a1s])
+    roots = ctx.trace_commit_batch(traces, log_blowup, offset)
+    alphas = []
+    for root, ch in zip(roots, channels):
+        ch.send(root.hex().encode())
+        alphas.append([ch.receive_random_field_element() for _ in range(3)])
+    res = ctx.fibsq_composition_commit_batch(log_t, log_blowup, traces[:, -1], alphas, offset,
+                                             channel_states=[bytes.fromhex(ch.state) for ch in channels])
+    gen = ctx.batch_info()[0]
+    fris = []
+    for b, (r, ch) in enumerate(zip(res, channels)):
+        fri = _mirror_commit(r, BatchMember(ctx, b), L, ch, generation=gen)
+        fri.member = b
+        fris.append(fri)
+    queries = [[] for _ in a1s]
+    for _ in range(num_queries):
+        idx = [ch.receive_random_int(0, n - 2 * B - 1, True) for ch in channels]
+        values, paths, lens = ctx.batch_query_round(idx, trace_count=3, trace_stride=B)
+        for b, (fri, ch) in enumerate(zip(fris, channels)):
+            queries[b].append(idx[b])
+            trace, openings = batch_round_records(values[b], paths[b], lens[b], 3, fri.n_layers, L)
+            for v, path in trace:
+                ch.send(v.to_bytes(8, "big"))
+                ch.send(path)
+            _send_openings(openings, ch)
+    return [StarkProof(roots[b], alphas[b], int(traces[b, -1]), fris[b], log_t, log_blowup, queries[b])
+            for b in range(len(a1s))]
 
 
 def fri_commit_sharded(coeffs: Sequence[int], log_n: int, channel: Channel, ctx: Context,

@@ -13,6 +13,19 @@ min(B, 64) of the members.  Every member has its own random coefficients on
 the device; (c)'s roots are checked against (a)'s for the members (a) ran.
 
     python tools/batch_probe.py [--reps 7] [--out profiles/commit_batch.txt]
+
+--prove: the batched prover against a loop of prove_fibsq, per proof.  For
+log_t in {7, 10, 13} at blowup 8, with 8 and 32 queries, through the Python
+mirror, warm, one process, the median of --reps runs, in microseconds per proof:
+  (a) a loop of prove_fibsq (over min(B, 16) members: its cost per proof does
+      not depend on B),
+  (b) prove_fibsq_batch of B = 16, 64, 256 members,
+each as the whole mirror call (trace on the host, channel hashing in Python
+included) and as the time inside its device calls alone; (b)'s device time is
+split into the trace commit, the composition commit and the query rounds.
+Every member's transcript of (b) is checked against (a)'s for the members (a) ran.
+
+    python tools/batch_probe.py --prove [--reps 7] [--out profiles/prove_batch.txt]
 """
 import argparse
 import ctypes
@@ -49,13 +62,128 @@ def med_us(fn, reps, per):
     return statistics.median(ts)
 
 
+PROVE_LOG_T = (7, 10, 13)
+PROVE_BATCHES = (16, 64, 256)
+PROVE_QUERIES = (8, 32)
+PROVE_LOG_BLOWUP = 3
+
+
+class TimedContext:
+    """A Context whose device calls of the two provers are timed, by group."""
+    GROUPS = {"trace_commit": "trace", "trace_commit_batch": "trace", "fibsq_composition_commit": "comp",
+              "fibsq_composition_commit_batch": "comp", "trace_decommit": "query", "decommit_query": "query",
+              "batch_decommit_query": "query", "batch_query_round": "query"}
+
+    def __init__(self, ctx):
+        self._ctx = ctx
+        self.reset()
+
+    def reset(self):
+        self.t = {"trace": 0.0, "comp": 0.0, "query": 0.0}
+
+    def __getattr__(self, name):
+        fn = getattr(self._ctx, name)
+        group = self.GROUPS.get(name)
+        if group is None:
+            return fn
+
+        def timed(*a, **k):
+            t0 = time.perf_counter()
+            try:
+                return fn(*a, **k)
+            finally:
+                self.t[group] += time.perf_counter() - t0
+        return timed
+
+
+def prove_mode(args, reps, say):
+    lib = fri_amd.load_library()
+    lb = PROVE_LOG_BLOWUP
+    ctx = TimedContext(fri_amd.Context(0, max(PROVE_LOG_T) + lb))
+    say(f"batch_probe --prove: {lib.fri_version().decode()}, blowup {1 << lb}, us per proof, median of {reps} "
+        "(warm, one process, Python mirror)")
+    say("(a) loop of prove_fibsq  (b) prove_fibsq_batch;  whole: the mirror call;  device: inside its device calls;")
+    say("trace / comp / query: (b)'s device time in fri_trace_commit_batch, fri_fibsq_composition_commit_batch and")
+    say("the fri_batch_query_round rounds")
+    say(f"{'log_t':>5} {'Q':>3} {'B':>4} {'(a) whole':>10} {'(a) device':>10} {'(b) whole':>10} {'(b) device':>10} "
+        f"{'trace':>8} {'comp':>8} {'query':>8} {'device (a)/(b)':>14}")
+    table = {}
+
+    def measure(fn, per):
+        whole, dev, parts = [], [], []
+        for _ in range(reps):
+            ctx.reset()
+            t0 = time.perf_counter()
+            fn()
+            whole.append((time.perf_counter() - t0) * 1e6 / per)
+            dev.append(sum(ctx.t.values()) * 1e6 / per)
+            parts.append(tuple(ctx.t[g] * 1e6 / per for g in ("trace", "comp", "query")))
+        i = sorted(range(reps), key=lambda j: dev[j])[reps // 2]
+        return statistics.median(whole), dev[i], parts[i]
+
+    for log_t in PROVE_LOG_T:
+        for Q in PROVE_QUERIES:
+            for B in PROVE_BATCHES:
+                a1s = [1000003 * b + 3141592 for b in range(B)]
+                m = min(B, 16)
+                proofs_a = []
+
+                def loop():
+                    proofs_a.clear()
+                    for b in range(m):
+                        ch = fri_amd.Channel()
+                        fri_amd.prove_fibsq(a1s[b], log_t, lb, Q, ch, ctx=ctx)
+                        proofs_a.append(ch.proof)
+
+                proofs_b = []
+
+                def batch():
+                    chans = [fri_amd.Channel() for _ in a1s]
+                    fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx)
+                    proofs_b[:] = [ch.proof for ch in chans[:m]]
+
+                loop()
+                batch()                               # warm: plans, graphs, the batch's buffers and tables
+                assert proofs_a == proofs_b, "batch and loop disagree"
+                aw, ad, _ = measure(loop, m)
+                bw, bd, (tr, co, qu) = measure(batch, B)
+                table[(log_t, Q, B)] = (ad, bd, aw, bw)
+                say(f"{log_t:>5} {Q:>3} {B:>4} {aw:>10.1f} {ad:>10.1f} {bw:>10.1f} {bd:>10.1f} {tr:>8.1f} {co:>8.1f} "
+                    f"{qu:>8.1f} {ad / bd:>13.1f}x")
+    say()
+    for log_t in PROVE_LOG_T:
+        for Q in PROVE_QUERIES:
+            ad, bd, aw, bw = table[(log_t, Q, 256)]
+            say(f"log_t {log_t}, {Q} queries, B = 256: (b) device {bd:.1f} us is "
+                f"{'faster' if bd < ad else 'SLOWER'} than (a) {ad:.1f} us per proof ({ad / bd:.1f}x); "
+                f"whole {bw:.1f} against {aw:.1f} us ({aw / bw:.1f}x)")
+            wins = [B for B in PROVE_BATCHES if table[(log_t, Q, B)][1] < table[(log_t, Q, B)][0]]
+            wins_w = [B for B in PROVE_BATCHES if table[(log_t, Q, B)][3] < table[(log_t, Q, B)][2]]
+            say(f"    (b) beats (a) from B = {min(wins) if wins else 'none measured'} (device), "
+                f"{min(wins_w) if wins_w else 'none measured'} (whole)")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--logs", type=int, nargs="*", default=list(LOGS))
+    ap.add_argument("--prove", action="store_true", help="the batched prover against a loop of prove_fibsq")
     args = ap.parse_args()
     reps = max(args.reps, 5)
+    if args.prove:
+        lines = []
+
+        def say_p(s=""):
+            print(s, flush=True)
+            lines.append(s)
+
+        prove_mode(args, reps, say_p)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     lines = []
 
     def say(s=""):
