@@ -595,6 +595,90 @@ int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* 
                           uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
                           size_t paths_stride, size_t* paths_len);
 
+/* Batched verifier: `batch` transcripts of one shape checked in one call, the
+ * counterpart of the batched prover.  verify_fri / verify_fibsq of the host
+ * mirrors (one transcript, SHA-256 on one CPU core) stay the yardstick: for
+ * every transcript the verdict here is 0 exactly when they return true.
+ *
+ * How it runs.  A transcript carries the challenges and
+ * query indices it claims, so two independent kernels decide it: one lane per
+ * member replays the Fiat-Shamir channel (channel.rs:35-84) over the whole
+ * transcript and checks that every claimed alpha, beta and index is the one the
+ * replay draws; one lane per opening checks every authentication path, fold,
+ * final value and composition against the claimed values.  A member is
+ * accepted when neither finds anything.  Every check runs for every member:
+ * verdict[b] is the OR of the failed classes below, 0 = accepted.
+ *
+ * Record layout (host pointers).  Member b's head at head + b*head_stride
+ * (words): with trace_count = 3 the trace root (8 big-endian digest words) and
+ * the 3 claimed alphas; then max_layers roots of 8 words; max_layers - 1
+ * claimed betas; the final value.  A member with fewer layers fills a prefix
+ * of the roots and of the betas (the rest is not read).  A root is its 32 raw
+ * bytes: the message on the wire is their 64-character lowercase hex.  Member
+ * b's query q: the claimed index at indices[b*num_queries + q] and the record
+ * fri_batch_query_round writes, at values + (b*num_queries + q)*values_stride
+ * (words: trace_count trace values, then 2 * n_layers(b) FRI values in
+ * fri_decommit_query's order) and paths + (b*num_queries + q)*paths_stride
+ * (bytes: trace_count paths of 32*log_n bytes, then the FRI paths in
+ * fri_decommit_query's layout).  chan_in[b]: the channel before the member's
+ * first message.
+ *
+ * Numbers taken from a transcript only choose left/right in a path climb and
+ * exponents of domain points (indices are taken mod the layer size, trace
+ * positions mod 2^log_n); they never form an address.
+ *
+ * FRI_EINVAL, with nothing written: a shape outside the limits in
+ * fri_verify_shape, strides below the record's size, batch outside 1..65535,
+ * n_layers[b] outside 1..max_layers, offset or a_last[b] >= p, a multi-GPU
+ * context.  FRI_ENOMEM (one member's staging does not fit) leaves the context
+ * usable.  Otherwise FRI_OK, whatever the verdicts.  The members are uploaded
+ * and checked in chunks of a 2 GiB staging budget, one launch pair each
+ * (fri_debug_set_verify_chunk: members per chunk, 0 = by the budget); the
+ * staging belongs to the context and stays until fri_ctx_destroy.  The two
+ * kernels run on two streams joined by events; FRI_VERIFY_SERIAL=1
+ * (environment, a measurement hook) runs them one after the other, as a
+ * profiling context does (classes "verify_chain" and "verify_open").  The
+ * call reads and changes nothing of the resident commit, batch or trace
+ * batch: the commit generation does not move.
+ *
+ * Measured (tools/batch_probe.py --verify, profiles/verify_batch.txt, DESIGN.md
+ * section 4g; us per proof, blowup 8, the device call with its copies against a
+ * loop of the C++ verify_fibsq on one core / over 16 threads): at log_t 7 with 8
+ * queries 591 at B = 16, 31.2 at 256 and 2.6 at 4096 against 308 / 22.0; at log_t 13
+ * with 32 queries 5162, 244 and 21.1 against 2367 / 152.  One lane hashes a whole
+ * transcript, so the channel kernel runs for milliseconds whatever the batch: the
+ * call loses to one core below B = 64 and to 16 threads below B = 4096. */
+#define FRI_VERIFY_MAX_QUERIES 1024
+#define FRI_VERIFY_CHANNEL      1u   /* a claimed alpha, beta or query index is not what the replayed channel draws */
+#define FRI_VERIFY_TRACE_PATH   2u   /* a trace opening does not reach the trace root                               */
+#define FRI_VERIFY_COMPOSITION  4u   /* layer 0 at the query is not the composition of the opened f(x), f(gx), f(g^2 x) */
+#define FRI_VERIFY_FRI_PATH     8u   /* a layer opening does not reach its layer root                              */
+#define FRI_VERIFY_FOLD        16u   /* a layer-k value is not the fold of its layer-(k-1) pair                    */
+#define FRI_VERIFY_FINAL       32u   /* the last layer's pair is not the final value                               */
+#define FRI_VERIFY_MALFORMED   64u   /* a packed word >= p, or (set by the host mirrors) a transcript that cannot be packed */
+typedef struct {
+    uint32_t log_n;        /* layer 0 has 2^log_n values; 1..min(30, ctx log_n_max) */
+    uint32_t max_layers;   /* record stride in layers, 1..log_n+1                   */
+    uint32_t num_queries;  /* 0..FRI_VERIFY_MAX_QUERIES                             */
+    uint32_t trace_count;  /* 0: FRI only (verify_fri); 3: STARK-101 FibonacciSq    */
+    uint32_t log_t, log_blowup;   /* trace_count = 3: log_n = log_t + log_blowup,
+                                     log_t >= 2, log_blowup 1..4                    */
+    uint32_t offset;       /* coset offset, canonical                               */
+    uint64_t max_index;    /* the query draw's upper bound (verify_fri's max_index,
+                              below 2^32; 2^log_n - 2*2^log_blowup - 1 when
+                              trace_count = 3)                                      */
+} fri_verify_shape;
+int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uint32_t batch,
+                     const fri_channel_state* chan_in,   /* [batch] */
+                     const uint32_t* n_layers,           /* [batch], 1..max_layers */
+                     const uint32_t* a_last,             /* [batch] when trace_count = 3, else NULL */
+                     const uint32_t* head, size_t head_stride,      /* words  */
+                     const uint64_t* indices,                        /* [batch][num_queries] claimed */
+                     const uint32_t* values, size_t values_stride,  /* words per (member, query) */
+                     const uint8_t* paths, size_t paths_stride,     /* bytes per (member, query) */
+                     uint32_t* verdict);                             /* [batch] mask, 0 = accepted */
+int fri_debug_set_verify_chunk(fri_ctx* ctx, uint32_t members);    /* 0 = automatic */
+
 /* Which commit the read-backs below serve: `generation` grows with every
  * commit call on the context (successful or not), log_n / n_layers describe
  * the resident commit (n_layers = 0 when the last commit failed).  A binding

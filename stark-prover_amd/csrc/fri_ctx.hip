@@ -100,6 +100,7 @@ extern "C" int fri_ctx_destroy(fri_ctx* ctx) {
     if (ctx->h2d_stream) hipStreamSynchronize(ctx->h2d_stream);
     plan_free(ctx);
     batch_free(ctx);
+    verify_free(ctx);
     for (Lane& ln : ctx->lanes) {
         if (ln.stream) hipStreamDestroy(ln.stream);
         dfree(ctx, ln.d_state);

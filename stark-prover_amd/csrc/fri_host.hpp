@@ -12,6 +12,7 @@
 //   fri_batch.hip      the batched commit of many small codewords, its
 //                      member-wise read-backs and the batched prover entry
 //                      points (trace commit, composition commit, query round)
+//   fri_verify.hip     the batched verifier: staging, chunking, the launch pair
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
 //                      which commit the read-backs serve (residency)
 //   fri_readback.hip   read-backs, decommitment and the prover entry points
@@ -160,6 +161,18 @@ struct Batch {
     size_t h_q_cap = 0;
 };
 
+// The batched verifier (fri_verify_batch, fri_verify.hip): one device buffer
+// for a chunk of packed transcripts (grown on demand, kept until
+// fri_ctx_destroy), a second stream for k_verify_open and the events that
+// join it to the context stream.
+struct VerifyBufs {
+    uint8_t* dev = nullptr;
+    size_t cap = 0;              // bytes
+    hipStream_t side = nullptr;
+    hipEvent_t ev_up = nullptr, ev_open = nullptr;
+    uint32_t chunk = 0;          // fri_debug_set_verify_chunk: members per launch pair (0: by byte budget)
+};
+
 struct Team;   // in-process team (defined below)
 
 // Collective transport of the sharded commit: RCCL on the context stream, or
@@ -299,6 +312,7 @@ struct fri_ctx {
     uint64_t commit_gen = 0;        // bumped by every commit: read-backs of an older proof are refused
     uint32_t commit_log_n = 0;      // codeword log2 of the resident commit
     Batch batch;                    // fri_commit_batch: buffers and residency (fri_batch.hip)
+    VerifyBufs verify;              // fri_verify_batch: staging (fri_verify.hip)
     uint32_t* interp_tmp = nullptr; // partials of fri_interpolate_points / fri_evaluate, fri_merkle_root's tree (grown on use)
     size_t interp_cap = 0;
     uint32_t roots_leaf = 0;        // fri_debug_set_roots_leaf: roots per leaf subtree (0: FRI_ROOTS_LEAF)
@@ -614,6 +628,9 @@ int no_layer(fri_ctx* ctx, const char* what);
 
 // ---- fri_batch.hip
 void batch_free(fri_ctx* ctx);                // fri_ctx_destroy
+
+// ---- fri_verify.hip
+void verify_free(fri_ctx* ctx);               // fri_ctx_destroy
 
 int input_checksum(fri_ctx* ctx, const uint32_t* d_src, size_t d, uint64_t* out);   // (synchronous)
 

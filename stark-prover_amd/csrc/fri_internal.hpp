@@ -361,4 +361,32 @@ struct BatchQuery {
 };
 void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s);
 
+// fri_verify_kernels.hip — the batched verifier (fri_verify_batch): `members`
+// transcripts of one shape, packed as fri_amd.h describes, in device memory
+// with compact strides.  Both kernels OR what they find into verdict[b]
+// (FRI_VERIFY_* bits); neither reads what the other writes.
+constexpr uint32_t VERIFY_MAX_LOG = 30;
+enum : uint32_t {                // FRI_VERIFY_* of fri_amd.h (fri_verify.hip asserts they agree)
+    VB_CHANNEL = 1, VB_TRACE_PATH = 2, VB_COMPOSITION = 4, VB_FRI_PATH = 8, VB_FOLD = 16, VB_FINAL = 32,
+    VB_MALFORMED = 64
+};
+struct VerifyTask {
+    const uint32_t* head;        // per member: [trace root 8, alphas 3] roots 8 * max_layers, betas, final
+    const uint32_t* chan;        // per member: fri_channel_state, 9 words (digest bytes, has_state)
+    const uint32_t* n_layers;    // per member, 1..max_layers
+    const uint32_t* a_last;      // per member (trace_count = 3)
+    const uint64_t* indices;     // [member][query], claimed
+    const uint32_t* values;      // [member][query] records of val_words words
+    const uint32_t* paths;       // [member][query] records of path_words words (the bytes as they are sent)
+    uint32_t* verdict;
+    uint32_t head_words, val_words, path_words;
+    uint32_t members, log_n, max_layers, num_queries, trace_count, log_t, log_blowup;
+    uint64_t range;              // max_index + 1, <= 2^32
+    uint32_t glast_m, gprev_m;   // Montgomery(g^{T-1}), Montgomery(g^{T-2}), g = w_T (trace_count = 3)
+    // Montgomery(w_{2^(log_n-k)}) and Montgomery(offset^(2^k)): layer k lives on offset^(2^k) <w_{2^(log_n-k)}>
+    uint32_t w_m[VERIFY_MAX_LOG + 1], off_m[VERIFY_MAX_LOG + 1];
+};
+void launch_verify_chain(const VerifyTask& t, hipStream_t s);
+void launch_verify_open(const VerifyTask& t, hipStream_t s);
+
 }  // namespace fri

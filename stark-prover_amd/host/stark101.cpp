@@ -961,6 +961,226 @@ bool verify_fibsq(const Msgs& msgs, FE a_last, uint32_t log_t, uint32_t log_blow
     return verify_transcript(msgs, L, n_layers, num_queries, n - 2 * B - 1, offset, channel_state, pre, on_query);
 }
 
+// ------------------------------------------------------- batched verifier
+namespace {
+// Transcripts of one shape in fri_verify_batch's record layout (fri_amd.h).
+struct Packed {
+    fri_verify_shape sh{};
+    size_t hw = 0, vw = 0, pb = 0;             // head words, values words, paths bytes per record
+    std::vector<fri_channel_state> chan;
+    std::vector<uint32_t> n_layers, a_last, head, values;
+    std::vector<uint64_t> indices;
+    std::vector<uint8_t> paths;
+    std::vector<uint32_t> reasons;             // a host decision (FRI_VERIFY_MALFORMED) or 0
+    std::vector<uint8_t> host;                 // 1: left to the host verifier
+};
+enum class PackRc { Ok, Malformed, Host };
+
+bool canonical_hex(const std::vector<uint8_t>& m) {
+    for (uint8_t c : m)
+        if (!((c >= '0' && c <= '9') || (c >= 'a' && c <= 'f'))) return false;
+    return true;
+}
+
+// Member b's messages into its records.  Malformed: what verify_transcript
+// certainly rejects (a wrong message count for n_layers, a message of the
+// wrong length, a value, challenge or final value >= p, a one-element layer
+// whose doubled value differs).  Host: a root message that is not canonical
+// lowercase hex cannot be packed as raw bytes (and a final value >= p that no
+// query compares): the host verifier decides.
+PackRc pack_member(Packed& pk, size_t b, const Msgs& msgs, size_t nl, const std::string& state) {
+    const uint32_t L = pk.sh.log_n, ML = pk.sh.max_layers, Q = pk.sh.num_queries, tc = pk.sh.trace_count;
+    if (nl == 0 || nl > L + 1u) return PackRc::Malformed;
+    size_t per_q = 1 + 2 * tc;
+    for (size_t k = 0; k < nl; k++) per_q += (L - k == 0) ? 5 : 4;
+    if (msgs.size() != (tc ? 4 : 0) + 2 * nl + Q * per_q) return PackRc::Malformed;
+    const size_t hb = tc ? 11 : 0;
+    uint32_t* head = pk.head.data() + b * pk.hw;
+    size_t pos = 0;
+    bool malformed = false, to_host = false;
+    auto value = [&](uint32_t& out) {
+        const auto& m = msgs[pos++];
+        const uint64_t v = m.size() == 8 ? be_u64(m) : P;
+        if (v >= P) malformed = true;
+        else out = static_cast<uint32_t>(v);
+    };
+    auto root = [&](uint32_t* out) {
+        const auto& m = msgs[pos++];
+        if (m.size() != 64) { malformed = true; return; }
+        if (!canonical_hex(m)) { to_host = true; return; }
+        const auto raw = sha::from_hex(std::string(m.begin(), m.end()));
+        for (int i = 0; i < 8; i++)
+            out[i] = uint32_t{raw[4 * i]} << 24 | uint32_t{raw[4 * i + 1]} << 16 | uint32_t{raw[4 * i + 2]} << 8 | raw[4 * i + 3];
+    };
+    if (tc) {
+        root(head);
+        for (int j = 0; j < 3; j++) value(head[8 + j]);
+    }
+    for (size_t k = 0; k < nl; k++) {
+        root(head + hb + 8 * k);
+        if (k + 1 < nl) value(head[hb + 8 * ML + k]);
+    }
+    if (Q == 0 && msgs[pos].size() == 8 && be_u64(msgs[pos]) >= P) to_host = true;
+    value(head[hb + 9 * ML - 1]);
+    for (size_t q = 0; q < Q; q++) {
+        const auto& im = msgs[pos++];
+        if (im.size() != 8) malformed = true;
+        else pk.indices[b * Q + q] = be_u64(im);
+        uint32_t* vals = pk.values.data() + (b * Q + q) * pk.vw;
+        uint8_t* rec = pk.paths.data() + (b * Q + q) * pk.pb;
+        size_t off = 0;
+        auto path = [&](size_t depth) {
+            const auto& m = msgs[pos++];
+            if (m.size() != 32 * depth) { malformed = true; return; }
+            if (!m.empty()) std::memcpy(rec + off, m.data(), m.size());
+            off += 32 * depth;
+        };
+        for (size_t j = 0; j < tc; j++) {
+            value(vals[j]);
+            path(L);
+        }
+        for (size_t k = 0; k < nl; k++) {
+            const size_t depth = L - k;
+            if (depth == 0 && msgs[pos] != msgs[pos + 1]) malformed = true;
+            if (depth == 0) pos++;
+            value(vals[tc + 2 * k]);
+            path(depth);
+            value(vals[tc + 2 * k + 1]);
+            path(depth);
+        }
+    }
+    if (malformed) return PackRc::Malformed;       // certain, whatever else the transcript holds
+    if (to_host) return PackRc::Host;
+    if (!state.empty()) {
+        const auto st = sha::from_hex(state);
+        if (st.size() != 32) throw Panic("verify batch: a channel state is \"\" or 64 hex characters");
+        std::memcpy(pk.chan[b].digest, st.data(), 32);
+        pk.chan[b].has_state = 1;
+    }
+    pk.n_layers[b] = static_cast<uint32_t>(nl);
+    return PackRc::Ok;
+}
+
+Packed pack_batch(const std::vector<Msgs>& t, uint32_t log_n, const std::vector<size_t>& n_layers, size_t num_queries,
+                  size_t max_index, uint32_t tc, uint32_t log_t, uint32_t log_blowup, FE offset,
+                  const std::vector<std::string>& states) {
+    const size_t B = t.size();
+    Packed pk;
+    size_t ML = 1;
+    for (size_t nl : n_layers)
+        if (nl <= log_n + 1u) ML = std::max(ML, nl);
+    pk.sh.log_n = log_n;
+    pk.sh.max_layers = static_cast<uint32_t>(ML);
+    pk.sh.num_queries = static_cast<uint32_t>(num_queries);
+    pk.sh.trace_count = tc;
+    pk.sh.log_t = log_t;
+    pk.sh.log_blowup = log_blowup;
+    pk.sh.offset = static_cast<uint32_t>(offset.value());
+    pk.sh.max_index = max_index;
+    pk.hw = (tc ? 11 : 0) + 9 * ML;
+    pk.vw = tc + 2 * ML;
+    pk.pb = size_t{tc} * 32 * log_n;
+    for (size_t k = 0; k < ML; k++) pk.pb += 64 * (log_n - k);
+    const size_t Q = num_queries;
+    pk.chan.assign(B, fri_channel_state{});
+    pk.n_layers.assign(B, 1);
+    pk.a_last.assign(B, 0);
+    pk.head.assign(B * pk.hw, 0);
+    pk.values.assign(B * Q * pk.vw + 1, 0);
+    pk.indices.assign(B * Q + 1, 0);
+    pk.paths.assign(B * Q * pk.pb + 1, 0);
+    pk.reasons.assign(B, 0);
+    pk.host.assign(B, 0);
+    for (size_t b = 0; b < B; b++) {
+        const PackRc rc = pack_member(pk, b, t[b], n_layers[b], states.empty() ? std::string() : states[b]);
+        if (rc == PackRc::Ok) continue;
+        // a member decided on the host holds zeros and one layer
+        std::fill(pk.head.begin() + b * pk.hw, pk.head.begin() + (b + 1) * pk.hw, 0u);
+        std::fill(pk.values.begin() + b * Q * pk.vw, pk.values.begin() + (b + 1) * Q * pk.vw, 0u);
+        std::fill(pk.indices.begin() + b * Q, pk.indices.begin() + (b + 1) * Q, uint64_t{0});
+        std::fill(pk.paths.begin() + b * Q * pk.pb, pk.paths.begin() + (b + 1) * Q * pk.pb, uint8_t{0});
+        if (rc == PackRc::Malformed) pk.reasons[b] = FRI_VERIFY_MALFORMED;
+        else pk.host[b] = 1;
+    }
+    return pk;
+}
+
+// The masks of a packed batch: the packer's decisions, host_verify(b) for the
+// members it left to the host verifier, the device's for every other member.
+std::vector<bool> verify_packed(Packed& pk, const std::function<bool(size_t)>& host_verify, std::shared_ptr<Gpu> gpu,
+                                std::vector<uint32_t>* reasons, const char* what) {
+    const size_t B = pk.reasons.size(), Q = pk.sh.num_queries;
+    std::vector<uint32_t> mask = pk.reasons;
+    bool device = false;
+    for (size_t b = 0; b < B; b++) device = device || (!pk.reasons[b] && !pk.host[b]);
+    if (device) {
+        const uint32_t L = pk.sh.log_n;
+        if (!gpu) {
+            gpu = Gpu::thread_default(L);
+            if (gpu->n_ranks() > 1) gpu = beside_team(L);        // the verifier runs on one device
+        }
+        if (gpu->n_ranks() > 1) throw Panic(std::string(what) + ": batches run on a one-device Gpu");
+        if (L > gpu->log_n_max()) throw Panic(std::string(what) + ": 2^" + std::to_string(L) + " exceeds the context");
+        std::vector<uint32_t> got(B, 0);
+        for (size_t b0 = 0; b0 < B; b0 += 65535) {
+            const size_t m = std::min<size_t>(65535, B - b0);
+            gpu->check(fri_verify_batch(gpu->ctx(), &pk.sh, static_cast<uint32_t>(m), pk.chan.data() + b0,
+                                        pk.n_layers.data() + b0, pk.sh.trace_count ? pk.a_last.data() + b0 : nullptr,
+                                        pk.head.data() + b0 * pk.hw, pk.hw, pk.indices.data() + b0 * Q,
+                                        pk.values.data() + b0 * Q * pk.vw, pk.vw, pk.paths.data() + b0 * Q * pk.pb,
+                                        std::max<size_t>(pk.pb, 1), got.data() + b0),
+                       "fri_verify_batch");
+        }
+        for (size_t b = 0; b < B; b++)
+            if (!pk.reasons[b] && !pk.host[b]) mask[b] = got[b];
+    }
+    for (size_t b = 0; b < B; b++)
+        if (pk.host[b]) mask[b] = host_verify(b) ? 0u : uint32_t{FRI_VERIFY_MALFORMED};
+    if (reasons) *reasons = mask;
+    std::vector<bool> ok(B);
+    for (size_t b = 0; b < B; b++) ok[b] = mask[b] == 0;
+    return ok;
+}
+}  // namespace
+
+std::vector<bool> verify_fri_batch(const std::vector<Msgs>& transcripts, uint32_t log_n,
+                                   const std::vector<size_t>& n_layers, size_t num_queries, size_t max_index, FE offset,
+                                   const std::vector<std::string>& channel_states, std::shared_ptr<Gpu> gpu,
+                                   std::vector<uint32_t>* reasons) {
+    const size_t B = transcripts.size();
+    if (n_layers.size() != B || (!channel_states.empty() && channel_states.size() != B))
+        throw Panic("verify_fri_batch: one n_layers and channel state per transcript");
+    if (reasons) reasons->clear();
+    if (B == 0) return {};
+    Packed pk = pack_batch(transcripts, log_n, n_layers, num_queries, max_index, 0, 0, 0, offset, channel_states);
+    auto host = [&](size_t b) {
+        return verify_fri(transcripts[b], log_n, n_layers[b], num_queries, max_index, offset,
+                          channel_states.empty() ? std::string() : channel_states[b]);
+    };
+    return verify_packed(pk, host, std::move(gpu), reasons, "verify_fri_batch");
+}
+
+std::vector<bool> verify_fibsq_batch(const std::vector<Msgs>& transcripts, const std::vector<FE>& a_last,
+                                     uint32_t log_t, uint32_t log_blowup, size_t num_queries,
+                                     const std::vector<size_t>& n_layers, FE offset,
+                                     const std::vector<std::string>& channel_states, std::shared_ptr<Gpu> gpu,
+                                     std::vector<uint32_t>* reasons) {
+    const size_t B = transcripts.size();
+    if (a_last.size() != B || n_layers.size() != B || (!channel_states.empty() && channel_states.size() != B))
+        throw Panic("verify_fibsq_batch: one a_last, n_layers and channel state per transcript");
+    if (reasons) reasons->clear();
+    if (B == 0) return {};
+    const uint32_t L = log_t + log_blowup;
+    const size_t max_index = (size_t{1} << L) - 2 * (size_t{1} << log_blowup) - 1;
+    Packed pk = pack_batch(transcripts, L, n_layers, num_queries, max_index, 3, log_t, log_blowup, offset, channel_states);
+    for (size_t b = 0; b < B; b++) pk.a_last[b] = static_cast<uint32_t>(a_last[b].value());
+    auto host = [&](size_t b) {
+        return verify_fibsq(transcripts[b], a_last[b], log_t, log_blowup, num_queries, n_layers[b], offset,
+                            channel_states.empty() ? std::string() : channel_states[b]);
+    };
+    return verify_packed(pk, host, std::move(gpu), reasons, "verify_fibsq_batch");
+}
+
 
 // ------------------------------------------------------- polynomial layer
 std::vector<FE> evaluate_on_coset(const Poly& poly, const Coset& coset) {

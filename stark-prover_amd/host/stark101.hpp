@@ -622,6 +622,29 @@ bool verify_fibsq(const std::vector<std::vector<uint8_t>>& messages, FE a_last, 
                   size_t num_queries, size_t n_layers, FE offset = FE(FRI_GENERATOR),
                   const std::string& channel_state = "");
 
+// verify_fri / verify_fibsq for many transcripts of one shape in ONE device
+// call (fri_verify_batch, include/fri_amd.h: one kernel replays every channel,
+// one lane per transcript, another checks every path, fold and composition
+// against the claimed challenges).  transcripts[b] has its own n_layers[b],
+// a_last[b] and channel_states[b] (empty vector: every channel starts empty).
+// The result is what a loop of verify_fri / verify_fibsq returns; `reasons`
+// receives the FRI_VERIFY_* masks (0 = accepted).  A transcript the host
+// verifier certainly rejects for its form (message count or lengths, a value,
+// challenge or final value >= p, a one-element layer whose doubled value
+// differs) is decided here with FRI_VERIFY_MALFORMED; one whose root messages
+// are not canonical lowercase hex goes to the host verifier.  Mismatched
+// lengths panic; an empty batch returns an empty vector.  Without a Gpu: the
+// thread's default, or the one-device Gpu beside a default team.
+std::vector<bool> verify_fri_batch(const std::vector<std::vector<std::vector<uint8_t>>>& transcripts, uint32_t log_n,
+                                   const std::vector<size_t>& n_layers, size_t num_queries, size_t max_index,
+                                   FE offset = FE(FRI_GENERATOR), const std::vector<std::string>& channel_states = {},
+                                   std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr);
+std::vector<bool> verify_fibsq_batch(const std::vector<std::vector<std::vector<uint8_t>>>& transcripts,
+                                     const std::vector<FE>& a_last, uint32_t log_t, uint32_t log_blowup,
+                                     size_t num_queries, const std::vector<size_t>& n_layers,
+                                     FE offset = FE(FRI_GENERATOR), const std::vector<std::string>& channel_states = {},
+                                     std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr);
+
 // ---------------------------------------------------- polynomial layer (GPU)
 // evaluate() at every coset point (fri_commit.rs:78): the LDE.
 std::vector<FE> evaluate_on_coset(const Poly& poly, const Coset& coset);

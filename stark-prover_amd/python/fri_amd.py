@@ -58,6 +58,10 @@ MP_FORCE_DIRECT = 2
 MP_SMALL_LEAF = 4         # FRI_MP_SMALL_LEAF: leaf subtrees of 64 points
 MP_EVAL_MIN = 65536       # FRI_MP_EVAL_MIN: evaluation takes the tree from min(d, count) >= this
 MP_INTERP_MIN = 65536     # FRI_MP_INTERP_MIN: arbitrary-point interpolation takes the tree from n >= this
+VERIFY_MAX_QUERIES = 1024   # FRI_VERIFY_MAX_QUERIES: queries per member of fri_verify_batch
+# FRI_VERIFY_*: the verdict bits of fri_verify_batch (0 = accepted)
+VERIFY_CHANNEL, VERIFY_TRACE_PATH, VERIFY_COMPOSITION, VERIFY_FRI_PATH = 1, 2, 4, 8
+VERIFY_FOLD, VERIFY_FINAL, VERIFY_MALFORMED = 16, 32, 64
 
 
 class FriError(RuntimeError):
@@ -77,6 +81,13 @@ class CommitResult(ctypes.Structure):
                 ("roots", (ctypes.c_uint8 * 32) * (MAX_ROUNDS + 1)),
                 ("betas", ctypes.c_uint32 * MAX_ROUNDS),
                 ("channel_out", ChannelState)]
+
+
+class VerifyShape(ctypes.Structure):
+    """fri_verify_shape: the shape every member of a fri_verify_batch shares."""
+    _fields_ = [("log_n", ctypes.c_uint32), ("max_layers", ctypes.c_uint32), ("num_queries", ctypes.c_uint32),
+                ("trace_count", ctypes.c_uint32), ("log_t", ctypes.c_uint32), ("log_blowup", ctypes.c_uint32),
+                ("offset", ctypes.c_uint32), ("max_index", ctypes.c_uint64)]
 
 
 class Collectives(ctypes.Structure):
@@ -202,6 +213,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                         ctypes.c_uint64, pu32, sz, ctypes.POINTER(ctypes.c_uint8), sz,
                                         ctypes.POINTER(sz)]),
         "fri_debug_transport_log": (i32, [vp, ctypes.POINTER(TransportOp), sz, ctypes.POINTER(sz)]),
+        "fri_verify_batch": (i32, [vp, ctypes.POINTER(VerifyShape), u32, ctypes.POINTER(ChannelState), pu32, pu32,
+                                   pu32, sz, ctypes.POINTER(ctypes.c_uint64), pu32, sz,
+                                   ctypes.POINTER(ctypes.c_uint8), sz, pu32]),
+        "fri_debug_set_verify_chunk": (i32, [vp, u32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -695,6 +710,29 @@ class Context:
         self.round_needed = int(ln[0]) if rc == FRI_EINVAL else 0     # (too-small strides: the needed paths stride)
         self._check(rc)
         return values, paths, [int(x) for x in ln][:batch]
+
+    def verify_batch(self, shape: "VerifyShape", batch: int, chan, n_layers, a_last, head, head_stride: int,
+                     indices, values, values_stride: int, paths, paths_stride: int, verdict=None) -> np.ndarray:
+        """fri_verify_batch over the raw ABI: ``shape`` a VerifyShape, ``chan``
+        a (batch, 36) uint8 array of fri_channel_state records, the other
+        arrays as fri_amd.h lays them out (``PackedTranscripts.abi_args()``
+        gives them all).  Returns the verdict masks, a uint32 array (the
+        caller's ``verdict`` when given): 0 = accepted, else VERIFY_* bits."""
+        if verdict is None:
+            verdict = np.zeros(max(batch, 1), dtype=np.uint32)
+        u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
+        rc = self.lib.fri_verify_batch(self.h, ctypes.byref(shape), batch,
+                                       chan.ctypes.data_as(ctypes.POINTER(ChannelState)), _ptr(n_layers),
+                                       _ptr(a_last) if a_last is not None else None, _ptr(head), head_stride,
+                                       indices.ctypes.data_as(u64p), _ptr(values), values_stride,
+                                       paths.ctypes.data_as(u8p), paths_stride, _ptr(verdict))
+        self._check(rc)
+        return verdict[:batch]
+
+    def set_verify_chunk(self, members: int):
+        """fri_debug_set_verify_chunk: members per upload and launch pair of
+        later verify_batch calls (0: chosen by the staging budget)."""
+        self._check(self.lib.fri_debug_set_verify_chunk(self.h, members))
 
     def commit_info(self):
         """(generation, log_n, n_layers) of the resident commit (fri_commit_info)."""
@@ -1761,6 +1799,267 @@ def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queri
             _send_openings(openings, ch)
     return [StarkProof(roots[b], alphas[b], int(traces[b, -1]), fris[b], log_t, log_blowup, queries[b])
             for b in range(len(a1s))]
+
+
+# ---- batched verifier (fri_verify_batch) ------------------------------------
+_HEXDIGITS = frozenset(b"0123456789abcdef")
+
+
+@dataclass
+class PackedTranscripts:
+    """Transcripts of one shape in fri_verify_batch's record layout
+    (fri_amd.h), as pack_transcripts leaves them.  ``reasons[b]`` is a host
+    decision (VERIFY_MALFORMED) or 0; ``host[b]`` marks a member the existing
+    host verifier decides (its root messages are not canonical lowercase hex,
+    so they cannot be packed as raw bytes).  Both kinds hold zeros in the
+    arrays and n_layers 1."""
+    shape: VerifyShape
+    chan: np.ndarray          # (batch, 36) uint8: fri_channel_state
+    n_layers: np.ndarray      # (batch,) uint32
+    a_last: Optional[np.ndarray]   # (batch,) uint32 when trace_count = 3
+    head: np.ndarray          # (batch, head_stride) uint32
+    indices: np.ndarray       # (batch, num_queries) uint64
+    values: np.ndarray        # (batch, num_queries, values_stride) uint32
+    paths: np.ndarray         # (batch, num_queries, paths_stride) uint8
+    reasons: np.ndarray       # (batch,) uint32
+    host: np.ndarray          # (batch,) bool
+
+    @property
+    def batch(self) -> int:
+        return int(self.n_layers.size)
+
+    def abi_args(self) -> tuple:
+        """Context.verify_batch's arguments after ``self``, without verdict."""
+        return (self.shape, self.batch, self.chan, self.n_layers, self.a_last, self.head, self.head.shape[1],
+                self.indices, self.values, self.values.shape[2], self.paths, self.paths.shape[2])
+
+
+def verify_record_strides(log_n: int, max_layers: int, trace_count: int) -> tuple:
+    """(head words, values words, paths bytes) of one member's head and of one
+    (member, query) record: the query record is fri_batch_query_round's."""
+    return ((11 if trace_count else 0) + 9 * max_layers, trace_count + 2 * max_layers,
+            32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(max_layers)))
+
+
+def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layers: Sequence[int], num_queries: int,
+                     max_index: int, trace_count: int = 0, log_t: int = 0, log_blowup: int = 0,
+                     a_last: Optional[Sequence[int]] = None, offset: int = GENERATOR,
+                     channel_states: Optional[Sequence[str]] = None) -> PackedTranscripts:
+    """Pure host code: the messages of verify_fri (trace_count 0) or
+    verify_fibsq (trace_count 3) transcripts into fri_verify_batch's arrays.
+    A member is decided here only where the host verifier certainly rejects
+    it (VERIFY_MALFORMED in ``reasons``): a wrong message count for its
+    n_layers, a message of the wrong length, a value, challenge or final value
+    >= p, a one-element layer whose doubled value differs.  A member whose
+    root messages are not canonical lowercase hex is left to the host verifier
+    (``host``), as is the one case _verify_transcript does not settle by
+    length, an FRI value that is not 8 bytes."""
+    B = len(transcripts)
+    if len(n_layers) != B or (channel_states is not None and len(channel_states) != B) or \
+            (trace_count and (a_last is None or len(a_last) != B)):
+        raise FriError(FRI_EINVAL, "one n_layers, a_last and channel state per transcript")
+    if trace_count not in (0, 3):
+        raise FriError(FRI_EINVAL, "trace_count must be 0 or 3")
+    L, Q, tc = log_n, num_queries, trace_count
+    ok_nl = [nl for nl in n_layers if 1 <= nl <= L + 1]
+    ML = max(ok_nl, default=1)
+    hw, vw, pb = verify_record_strides(L, ML, tc)
+    hb = 11 if tc else 0
+    shape = VerifyShape(L, ML, Q, tc, log_t, log_blowup, offset % (1 << 32), max_index)
+    pk = PackedTranscripts(shape, np.zeros((B, 36), np.uint8), np.ones(B, np.uint32),
+                           np.zeros(B, np.uint32) if tc else None, np.zeros((B, hw), np.uint32),
+                           np.zeros((B, Q), np.uint64), np.zeros((B, Q, vw), np.uint32),
+                           np.zeros((B, Q, max(pb, 1)), np.uint8), np.zeros(B, np.uint32), np.zeros(B, bool))
+
+    class _Malformed(Exception):
+        pass
+
+    class _Host(Exception):
+        pass
+
+    def u64(m: bytes, what_host: bool = False) -> int:
+        if len(m) != 8:
+            raise (_Host if what_host else _Malformed)()
+        v = int.from_bytes(m, "big")
+        if v >= P:
+            raise _Malformed()
+        return v
+
+    def root_words(m: bytes):
+        if len(m) != 64:
+            raise _Malformed()
+        if not all(c in _HEXDIGITS for c in m):
+            raise _Host()
+        return np.frombuffer(bytes.fromhex(m.decode()), dtype=">u4")
+
+    for b, msgs in enumerate(transcripts):
+        msgs, nl = list(msgs), n_layers[b]
+        try:
+            if not 1 <= nl <= L + 1:
+                raise _Malformed()
+            per_q = 1 + 2 * tc + sum(5 if L - k == 0 else 4 for k in range(nl))
+            if len(msgs) != (4 if tc else 0) + 2 * nl + Q * per_q:
+                raise _Malformed()
+            head, idxs, vals, pths = np.zeros(hw, np.uint32), [], np.zeros((Q, vw), np.uint32), []
+            it = iter(msgs)
+            if tc:
+                head[0:8] = root_words(next(it))
+                for j in range(3):
+                    head[8 + j] = u64(next(it))
+            for k in range(nl):
+                head[hb + 8 * k:hb + 8 * k + 8] = root_words(next(it))
+                if k < nl - 1:
+                    head[hb + 8 * ML + k] = u64(next(it))
+            fin = next(it)
+            if Q == 0 and len(fin) == 8 and int.from_bytes(fin, "big") >= P:
+                raise _Host()                 # no query ever compares it
+            head[hb + 9 * ML - 1] = u64(fin)
+            for q in range(Q):
+                m = next(it)
+                if len(m) != 8:
+                    raise _Malformed()
+                idxs.append(int.from_bytes(m, "big"))
+                rec = bytearray()
+                for j in range(tc):
+                    vals[q, j] = u64(next(it))
+                    path = next(it)
+                    if len(path) != 32 * L:
+                        raise _Malformed()
+                    rec += path
+                for k in range(nl):
+                    depth = L - k
+                    extra = next(it) if depth == 0 else None
+                    vb, path, sb, spath = next(it), next(it), next(it), next(it)
+                    if extra is not None and extra != vb:
+                        raise _Malformed()
+                    if len(path) != 32 * depth or len(spath) != 32 * depth:
+                        raise _Malformed()
+                    vals[q, tc + 2 * k], vals[q, tc + 2 * k + 1] = u64(vb, True), u64(sb, True)
+                    rec += path + spath
+                pths.append(bytes(rec))
+        except _Malformed:
+            pk.reasons[b] = VERIFY_MALFORMED
+            continue
+        except _Host:
+            pk.host[b] = True
+            continue
+        st = channel_states[b] if channel_states is not None else ""
+        if st:
+            pk.chan[b, :32] = np.frombuffer(bytes.fromhex(st), np.uint8)
+            pk.chan[b, 32] = 1
+        pk.n_layers[b] = nl
+        if tc:
+            pk.a_last[b] = int(a_last[b]) % P     # verify_fibsq reduces it too (fibsq_cp_at)
+        pk.head[b] = head
+        pk.values[b] = vals
+        for q in range(Q):
+            pk.indices[b, q] = idxs[q]
+            pk.paths[b, q, :len(pths[q])] = np.frombuffer(pths[q], np.uint8)
+    return pk
+
+
+def unpack_transcripts(pk: PackedTranscripts) -> List[Optional[List[bytes]]]:
+    """pack_transcripts' inverse: every packed member's messages (None for a
+    member decided on the host, whose record holds nothing)."""
+    sh = pk.shape
+    L, ML, Q, tc = sh.log_n, sh.max_layers, sh.num_queries, sh.trace_count
+    hb = 11 if tc else 0
+    out = []
+    for b in range(pk.batch):
+        if pk.reasons[b] or pk.host[b]:
+            out.append(None)
+            continue
+        nl, head, msgs = int(pk.n_layers[b]), pk.head[b], []
+        be = lambda v: int(v).to_bytes(8, "big")
+        root = lambda w: w.astype(">u4").tobytes().hex().encode()
+        if tc:
+            msgs.append(root(head[0:8]))
+            msgs += [be(head[8 + j]) for j in range(3)]
+        for k in range(nl):
+            msgs.append(root(head[hb + 8 * k:hb + 8 * k + 8]))
+            if k < nl - 1:
+                msgs.append(be(head[hb + 8 * ML + k]))
+        msgs.append(be(head[hb + 9 * ML - 1]))
+        for q in range(Q):
+            vals, raw = pk.values[b, q], pk.paths[b, q].tobytes()
+            msgs.append(be(pk.indices[b, q]))
+            for j in range(tc):
+                msgs += [be(vals[j]), raw[32 * L * j:32 * L * (j + 1)]]
+            off = 32 * L * tc
+            for k in range(nl):
+                pl = 32 * (L - k)
+                if L - k == 0:
+                    msgs.append(be(vals[tc + 2 * k]))
+                msgs += [be(vals[tc + 2 * k]), raw[off:off + pl], be(vals[tc + 2 * k + 1]), raw[off + pl:off + 2 * pl]]
+                off += 2 * pl
+        out.append(msgs)
+    return out
+
+
+def _verify_packed(pk: PackedTranscripts, host_verify, ctx: Optional[Context], reasons: Optional[list]) -> List[bool]:
+    """The masks of a packed batch: the host's decisions where the packer made
+    one, ``host_verify(b)`` where it left the member to the host verifier, the
+    device's for every other member (in calls of at most BATCH_MAX)."""
+    mask = pk.reasons.copy()
+    device = ~(pk.host | (pk.reasons != 0))
+    if device.any():
+        L = pk.shape.log_n
+        ctx = _beside_team(ctx or _default_ctx(L), L, _BATCH_CTX)     # the verifier runs on one device
+        args = pk.abi_args()
+        for b0 in range(0, pk.batch, BATCH_MAX):
+            b1 = min(pk.batch, b0 + BATCH_MAX)
+            got = ctx.verify_batch(args[0], b1 - b0, pk.chan[b0:b1], pk.n_layers[b0:b1],
+                                   pk.a_last[b0:b1] if pk.a_last is not None else None, pk.head[b0:b1], args[6],
+                                   pk.indices[b0:b1], pk.values[b0:b1], args[9], pk.paths[b0:b1], args[11])
+            mask[b0:b1] = np.where(device[b0:b1], got, mask[b0:b1])
+    for b in np.flatnonzero(pk.host):
+        mask[b] = 0 if host_verify(int(b)) else VERIFY_MALFORMED
+    if reasons is not None:
+        reasons[:] = [int(m) for m in mask]
+    return [bool(m == 0) for m in mask]
+
+
+def verify_fri_batch(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layers: Sequence[int], num_queries: int,
+                     max_index: int, offset: int = GENERATOR, channel_states: Optional[Sequence[str]] = None,
+                     ctx: Optional[Context] = None, reasons: Optional[list] = None) -> List[bool]:
+    """verify_fri for many transcripts of one shape (log_n, num_queries,
+    max_index, offset), member b with its own n_layers[b] and channel state,
+    in one device call (fri_verify_batch).  Returns what a loop of verify_fri
+    returns; ``reasons`` (a list) receives the VERIFY_* masks."""
+    if len(n_layers) != len(transcripts) or (channel_states is not None and len(channel_states) != len(transcripts)):
+        raise FriError(FRI_EINVAL, "one n_layers and channel state per transcript")
+    if len(transcripts) == 0:
+        if reasons is not None:
+            reasons[:] = []
+        return []
+    pk = pack_transcripts(transcripts, log_n, n_layers, num_queries, max_index, offset=offset,
+                          channel_states=channel_states)
+    state = lambda b: channel_states[b] if channel_states is not None else ""
+    return _verify_packed(pk, lambda b: verify_fri(transcripts[b], log_n, n_layers[b], num_queries, max_index, offset,
+                                                   state(b)), ctx, reasons)
+
+
+def verify_fibsq_batch(transcripts: Sequence[Sequence[bytes]], a_last: Sequence[int], log_t: int, log_blowup: int,
+                       num_queries: int, n_layers: Sequence[int], offset: int = GENERATOR,
+                       channel_states: Optional[Sequence[str]] = None, ctx: Optional[Context] = None,
+                       reasons: Optional[list] = None) -> List[bool]:
+    """verify_fibsq for many transcripts of one shape, member b with its own
+    a_last[b], n_layers[b] and channel state, in one device call.  Returns what
+    a loop of verify_fibsq returns; ``reasons`` receives the VERIFY_* masks."""
+    B = len(transcripts)
+    if len(a_last) != B or len(n_layers) != B or (channel_states is not None and len(channel_states) != B):
+        raise FriError(FRI_EINVAL, "one a_last, n_layers and channel state per transcript")
+    if B == 0:
+        if reasons is not None:
+            reasons[:] = []
+        return []
+    L = log_t + log_blowup
+    a_last = [int(a) % P for a in a_last]     # verify_fibsq reduces it (FE / fibsq_cp_at)
+    pk = pack_transcripts(transcripts, L, n_layers, num_queries, (1 << L) - 2 * (1 << log_blowup) - 1, 3, log_t,
+                          log_blowup, a_last, offset, channel_states)
+    state = lambda b: channel_states[b] if channel_states is not None else ""
+    return _verify_packed(pk, lambda b: verify_fibsq(transcripts[b], a_last[b], log_t, log_blowup, num_queries,
+                                                     n_layers[b], offset, state(b)), ctx, reasons)
 
 
 def fri_commit_sharded(coeffs: Sequence[int], log_n: int, channel: Channel, ctx: Context,

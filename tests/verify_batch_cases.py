@@ -1,0 +1,99 @@
+"""Transcripts for the batched verifier's tests (test_gpu_verify_batch.py,
+test_verify_batch_host.py): honest ones from the Python oracle, cached per
+process, forgeries built from oracle parts, and the class of every message of a
+transcript.  CPU code only, independent of the device."""
+import functools
+
+import fri_oracle as fo
+
+P = fo.P
+
+
+@functools.lru_cache(maxsize=None)
+def fibsq_case(a1, log_t, lb, queries, state=""):
+    """(messages, a_last, n_layers) of oracle.fibsq_prove from channel `state`."""
+    ch = fo.Channel(state=state)
+    pr = fo.fibsq_prove(a1, log_t, lb, queries, ch)
+    return tuple(ch.proof), fo.fibsq_trace(a1, 1 << log_t)[-1], len(pr.fri.roots)
+
+
+@functools.lru_cache(maxsize=None)
+def fri_case(seed, coeffs, log_n, queries, max_index, state=""):
+    """(messages, n_layers) of oracle.fri_commit + decommit_fri of `coeffs`
+    splitmix64 coefficients."""
+    ch = fo.Channel(state=state)
+    r = fo.fri_commit(fo.splitmix64_field(seed, coeffs), log_n, ch)
+    fo.decommit_fri(queries, max_index, r.layers, r.trees, ch)
+    return tuple(ch.proof), len(r.roots)
+
+
+def flip(msgs, i):
+    """msgs with message i's middle byte XOR 1."""
+    b = bytearray(msgs[i])
+    b[len(b) // 2] ^= 1
+    return list(msgs[:i]) + [bytes(b)] + list(msgs[i + 1:])
+
+
+def message_classes(log_n, n_layers, queries, trace_count):
+    """The class of every message of a transcript, in order: 'root', 'alpha',
+    'beta', 'final', 'index', 'trace_value', 'trace_path', 'value', 'path'."""
+    out = []
+    if trace_count:
+        out += ["root"] + ["alpha"] * 3
+    for k in range(n_layers):
+        out.append("root")
+        if k < n_layers - 1:
+            out.append("beta")
+    out.append("final")
+    for _ in range(queries):
+        out.append("index")
+        out += ["trace_value", "trace_path"] * trace_count
+        for k in range(n_layers):
+            if log_n - k == 0:
+                out.append("value")
+            out += ["value", "path", "value", "path"]
+    return out
+
+
+def forged_fibsq(log_t, lb, queries, a1=99, cp_seed=None, tweak=None, final_delta=0):
+    """A FibonacciSq transcript whose channel runs honestly over what the
+    prover chose to commit.  cp_seed: commit a low-degree polynomial unrelated
+    to the trace instead of the composition.  tweak(k, evals, last) -> evals:
+    what is committed as layer k instead of the honest evaluations (the
+    polynomial itself folds on honestly).  Returns (messages, a_last, n_layers)."""
+    L = log_t + lb
+    T, B, n = 1 << log_t, 1 << lb, 1 << L
+    trace = fo.fibsq_trace(a1, T)
+    f = fo.interpolate_lagrange_polynomials(fo.coset_domain(log_t, offset=1), trace, P)
+    fe = [fo.poly_evaluate(f, x, P) for x in fo.coset_domain(L)]
+    lv = fo.merkle_levels(fe)
+    ch = fo.Channel()
+    ch.send(lv[-1][0].hex().encode())
+    alphas = [ch.receive_random_field_element() for _ in range(3)]
+    poly = fo.splitmix64_field(cp_seed, T + 1) if cp_seed is not None else \
+        fo.fibsq_cp_faithful(f, log_t, trace[-1], alphas)
+    # fri_commit (fri_commit.rs:72-122) with the hook on what each layer commits
+    poly = fo.poly_trim(poly)
+    deg, domain, layers, trees, k = len(poly) - 1, fo.coset_domain(L), [], [], 0
+    while True:
+        evals = [fo.poly_evaluate(poly, x, P) for x in domain]
+        if tweak is not None:
+            evals = tweak(k, evals, deg < 1)
+        levels = fo.merkle_levels(evals)
+        layers.append(evals)
+        trees.append(levels)
+        ch.send(levels[-1][0].hex().encode())
+        if deg < 1:
+            break
+        beta = ch.receive_random_field_element()
+        poly, deg = fo.next_fri_polynomial(poly, deg, beta, P)
+        domain = [fo.fe_pow(x, 2, P) for x in domain[: len(domain) // 2]]
+        k += 1
+    ch.send(fo.fe_to_bytes(((0 if deg == -1 else poly[0]) + final_delta) % P))
+    for _ in range(queries):
+        idx = ch.receive_random_int(0, n - 2 * B - 1, True)
+        for j in range(3):
+            ch.send(fo.fe_to_bytes(fe[idx + j * B]))
+            ch.send(fo.merkle_proof(lv, idx + j * B))
+        fo.decommit_fri_layers(idx, layers, trees, ch)
+    return list(ch.proof), trace[-1], len(layers)

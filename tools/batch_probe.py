@@ -26,11 +26,27 @@ split into the trace commit, the composition commit and the query rounds.
 Every member's transcript of (b) is checked against (a)'s for the members (a) ran.
 
     python tools/batch_probe.py --prove [--reps 7] [--out profiles/prove_batch.txt]
+
+--verify: the batched verifier against loops of the host verifier, per proof.
+For log_t in {7, 13} at blowup 8, with 8 and 32 queries, B = 16, 64, 256, 4096
+transcripts from prove_fibsq_batch (min(B, 256) proved, repeated up to B), warm,
+the median of --reps runs, in microseconds per proof:
+  (a) fri_verify_batch, the device call with its copies (Context.verify_batch),
+      and the same call with FRI_VERIFY_SERIAL=1 (the two kernels on one stream);
+  (b) the two kernel classes alone (a profiling context: verify_chain, verify_open);
+  (c) packing in the C++ mirror: verify_fibsq_batch's whole call in
+      build/verify_native less (a);
+against a loop of the C++ verify_fibsq on one core and over 16 threads
+(build/verify_native, over min(B, 256) members).
+
+    python tools/batch_probe.py --verify [--reps 5] [--out profiles/verify_batch.txt]
 """
 import argparse
 import ctypes
+import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -164,14 +180,97 @@ def prove_mode(args, reps, say):
     ctx.close()
 
 
+VERIFY_SHAPES = ((7, 8), (7, 32), (13, 8), (13, 32))      # (log_t, queries)
+VERIFY_BATCHES = (16, 64, 256, 4096)
+VERIFY_THREADS = 16
+
+
+def verify_mode(args, reps, say):
+    lib = fri_amd.load_library()
+    lb = PROVE_LOG_BLOWUP
+    native = os.path.join(ROOT, "stark-prover_amd", "build", "verify_native")
+    ctx = fri_amd.Context(0, max(t for t, _ in VERIFY_SHAPES) + lb)
+    say(f"batch_probe --verify: {lib.fri_version().decode()}, blowup {1 << lb}, us per proof, median of {reps} "
+        "(warm; transcripts from prove_fibsq_batch)")
+    say("(a) fri_verify_batch with its copies, two streams / FRI_VERIFY_SERIAL=1   (b) kernel classes alone   "
+        "(c) packing in the C++ mirror")
+    say(f"loop 1 / loop {VERIFY_THREADS}: a loop of the C++ verify_fibsq on one core / over {VERIFY_THREADS} threads;  "
+        "min-max: the spread of (a) over the runs")
+    say(f"{'log_t':>5} {'Q':>3} {'B':>5} {'(a)':>9} {'(a) min-max':>15} {'(a) serial':>10} {'chain':>9} {'open':>9} "
+        f"{'(c) pack':>9} {'whole C++':>9} {'loop 1':>8} {'loop ' + str(VERIFY_THREADS):>8}")
+    table = {}
+    for log_t, Q in VERIFY_SHAPES:
+        L = log_t + lb
+        m = 256
+        a1s = [1000003 * b + 3141592 for b in range(m)]
+        chans = [fri_amd.Channel() for _ in a1s]
+        sps = fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx)
+        pk = fri_amd.pack_transcripts([ch.proof for ch in chans], L, [sp.fri.n_layers for sp in sps], Q,
+                                      (1 << L) - 2 * (1 << lb) - 1, 3, log_t, lb, [sp.a_last for sp in sps])
+        assert not pk.reasons.any() and not pk.host.any()
+        for B in VERIFY_BATCHES:
+            rep = -(-B // m)
+            cut = lambda a: np.ascontiguousarray(np.concatenate([a] * rep)[:B])   # noqa: E731
+            pb = fri_amd.PackedTranscripts(pk.shape, cut(pk.chan), cut(pk.n_layers), cut(pk.a_last), cut(pk.head),
+                                           cut(pk.indices), cut(pk.values), cut(pk.paths), cut(pk.reasons), cut(pk.host))
+            a = pb.abi_args()
+            call = lambda: ctx.verify_batch(*a)   # noqa: E731
+            assert not call().any(), "the device rejected an honest transcript"
+            ts = sorted(med_us(call, 1, B) for _ in range(reps))
+            dev, lo, hi = ts[reps // 2], ts[0], ts[-1]
+            os.environ["FRI_VERIFY_SERIAL"] = "1"
+            call()
+            serial = med_us(call, reps, B)
+            del os.environ["FRI_VERIFY_SERIAL"]
+            ctx.set_profiling(True)
+            ctx.reset_profile()
+            for _ in range(reps):
+                call()
+            chain, opn = (ctx.profile(c)[0] * 1e3 / reps / B for c in ("verify_chain", "verify_open"))
+            ctx.set_profiling(False)
+            out = subprocess.run([native, str(log_t), str(lb), str(Q), str(B), str(reps), str(VERIFY_THREADS)],
+                                 capture_output=True, text=True, timeout=1500)
+            nat = json.loads(out.stdout.strip().splitlines()[-1])
+            assert nat.get("accepted"), out.stdout + out.stderr
+            table[(log_t, Q, B)] = (dev, nat["loop_1"], nat["loop_n"], chain, opn, nat["batch_whole"], serial, lo, hi)
+            say(f"{log_t:>5} {Q:>3} {B:>5} {dev:>9.2f} {f'{lo:.2f}-{hi:.2f}':>15} {serial:>10.2f} {chain:>9.2f} "
+                f"{opn:>9.2f} {nat['batch_whole'] - dev:>9.2f} {nat['batch_whole']:>9.2f} {nat['loop_1']:>8.1f} "
+                f"{nat['loop_n']:>8.2f}")
+    say()
+    for log_t, Q in VERIFY_SHAPES:
+        for name, col in (("one core", 1), (f"{VERIFY_THREADS} threads", 2)):
+            wins = [B for B in VERIFY_BATCHES if table[(log_t, Q, B)][0] < table[(log_t, Q, B)][col]]
+            wins_w = [B for B in VERIFY_BATCHES if table[(log_t, Q, B)][5] < table[(log_t, Q, B)][col]]
+            say(f"log_t {log_t}, {Q} queries: the device call beats the loop on {name} from B = "
+                f"{min(wins) if wins else 'none measured'}; the whole C++ mirror call from B = "
+                f"{min(wins_w) if wins_w else 'none measured'}")
+        dev, _, _, chain, opn, _, serial, lo, hi = table[(log_t, Q, 256)]
+        say(f"    B = 256: two streams {dev:.2f} us (runs {lo:.2f}-{hi:.2f}), one stream {serial:.2f} us; kernels alone: "
+            f"chain {chain:.2f}, open {opn:.2f}")
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=None)
     ap.add_argument("--logs", type=int, nargs="*", default=list(LOGS))
     ap.add_argument("--prove", action="store_true", help="the batched prover against a loop of prove_fibsq")
+    ap.add_argument("--verify", action="store_true", help="the batched verifier against loops of verify_fibsq")
     args = ap.parse_args()
     reps = max(args.reps, 5)
+    if args.verify:
+        lines = []
+
+        def say_v(s=""):
+            print(s, flush=True)
+            lines.append(s)
+
+        verify_mode(args, reps, say_v)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.prove:
         lines = []
 
