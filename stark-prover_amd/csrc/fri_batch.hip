@@ -3,10 +3,11 @@
 // is a fixed number of launches, then ONE launch commits them all, one
 // workgroup per member (k_commit_batch, fri_layer.hip).  The batch has its
 // own buffers (Batch, fri_host.hpp): no lane's plan or graph is touched, so a
-// single commit afterwards replays what it captured.  Member-wise read-backs.
-// Below them the batched prover: B x fri_trace_commit, B x
-// fri_fibsq_composition_commit on that trace batch, and one query of every
-// member in one launch (fri_batch_query_round).
+// single commit afterwards replays what it captured.  The member-wise
+// read-backs are fri_readback.hip's.  Below the commit the batched prover:
+// B x fri_trace_commit, B x fri_fibsq_composition_commit on that trace batch
+// (the shape's checks and constants: fibsq_shape, fri_fibsq.hip), and one
+// query of every member in one launch (fri_batch_query_round).
 #include "fri_host.hpp"
 
 static_assert(FRI_BATCH_MAX_LOG_N >= 14 && FRI_BATCH_MAX_LOG_N <= (int)BATCH_MAX_LOG, "the kernel's tiles");
@@ -135,20 +136,12 @@ static void batch_lde(fri_ctx* ctx, const uint32_t* src, size_t src_stride, size
 // post-scale table is the context's (pow_lo / pow_hi), made on the stream.
 static void batch_intt(fri_ctx* ctx, const uint32_t* src, size_t src_stride, uint32_t* dst, size_t dst_stride,
                        uint32_t lg, uint32_t batch, uint32_t base, hipStream_t s) {
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, lg, base, inv_std((uint32_t)(((size_t)1 << lg) % P)), s);
-    if (lg <= BATCH_LDS_LDE_MAX_LOG) {
-        launch_batch_intt_lds(src, src_stride, dst, dst_stride, lg, batch, ctx->tw_inv, ctx->pow_lo, ctx->pow_hi, s);
+    if (lg > BATCH_LDS_LDE_MAX_LOG) {
+        coset_inverse(ctx, src, lg, base, 0, dst, batch, src_stride, dst_stride);
         return;
     }
-    NttPlan ip{};
-    ip.log_n = lg;
-    ip.tw = ctx->tw_inv;
-    ip.post_lo = ctx->pow_lo;
-    ip.post_hi = ctx->pow_hi;
-    ip.batch = batch;
-    ip.src_stride = src_stride;
-    ip.dst_stride = dst_stride;
-    launch_ntt(ip, src, (size_t)1 << lg, dst, s);
+    launch_pow_table(ctx->pow_lo, ctx->pow_hi, lg, base, post_scale(lg, 0), s);
+    launch_batch_intt_lds(src, src_stride, dst, dst_stride, lg, batch, ctx->tw_inv, ctx->pow_lo, ctx->pow_hi, s);
 }
 
 // keep_trace: the commit of a resident trace batch's composition (the trace
@@ -300,104 +293,6 @@ extern "C" int fri_batch_info(fri_ctx* ctx, uint64_t* generation, uint32_t* batc
     return FRI_OK;
 }
 
-// The resident batch's member: its copied-out state (n_layers = 0 when it failed).
-static int batch_member(fri_ctx* ctx, uint32_t member, const DevState** h) {
-    if (!ctx) return FRI_EINVAL;
-    const Batch& B = ctx->batch;
-    if (!B.resident)
-        return fail(ctx, FRI_ESTATE, "no resident batch: fri_batch_* serve the last fri_commit_batch until the next commit");
-    if (member >= B.count) return fail(ctx, FRI_EINVAL, "no such member");
-    *h = &B.b.h_states[member];
-    return FRI_OK;
-}
-
-extern "C" int fri_batch_layer_copy(fri_ctx* ctx, uint32_t member, uint32_t layer, uint32_t* out, size_t cap) {
-    if (!ctx || !out) return fail(ctx, FRI_EINVAL, "null argument");
-    const DevState* h;
-    int rc = batch_member(ctx, member, &h);
-    if (rc) return rc;
-    const Batch& B = ctx->batch;
-    if (layer >= h->n_layers) return fail(ctx, FRI_ESTATE, "no such committed layer of this member");
-    const size_t m = (size_t)1 << (B.log_n - layer);
-    if (cap < m) return fail(ctx, FRI_EINVAL, "output buffer too small");
-    FRI_HIP(ctx, hipSetDevice(ctx->device));
-    FRI_HIP(ctx, hipMemcpyAsync(out, B.b.words(BB_LAYERS) + member * B.lay_stride + B.lay.layer_off[layer], m * 4,
-                                hipMemcpyDeviceToHost, ctx->stream));
-    FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return FRI_OK;
-}
-
-extern "C" int fri_batch_tree_level_copy(fri_ctx* ctx, uint32_t member, uint32_t layer, uint32_t level, uint8_t* out,
-                                         size_t cap) {
-    if (!ctx || !out) return fail(ctx, FRI_EINVAL, "null argument");
-    const DevState* h;
-    int rc = batch_member(ctx, member, &h);
-    if (rc) return rc;
-    const Batch& B = ctx->batch;
-    if (layer >= h->n_layers) return fail(ctx, FRI_ESTATE, "no such committed layer of this member");
-    const uint32_t L = B.log_n - layer;
-    if (level > L) return fail(ctx, FRI_EINVAL, "level above root");
-    const size_t cnt = (size_t)1 << (L - level);
-    if (cap < cnt * 32) return fail(ctx, FRI_EINVAL, "output buffer too small");
-    std::vector<uint32_t> w(cnt * 8);
-    FRI_HIP(ctx, hipSetDevice(ctx->device));
-    FRI_HIP(ctx, hipMemcpyAsync(w.data(),
-                                B.b.words(BB_TREES) + member * B.tre_stride + B.lay.tree_off[layer] +
-                                    8 * level_offset(L, level),
-                                cnt * 32, hipMemcpyDeviceToHost, ctx->stream));
-    FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < cnt; i++) digest_to_bytes(&w[8 * i], out + 32 * i);
-    return FRI_OK;
-}
-
-extern "C" int fri_batch_commit_degrees(fri_ctx* ctx, uint32_t member, int32_t* out, size_t cap, uint32_t* n_out) {
-    if (!ctx || !n_out) return fail(ctx, FRI_EINVAL, "null argument");
-    const DevState* h;
-    int rc = batch_member(ctx, member, &h);
-    if (rc) return rc;
-    if (h->status) return fail(ctx, FRI_ESTATE, "this member's commit failed");
-    const uint32_t n = h->n_layers;
-    *n_out = n;
-    if (n && (!out || cap < n)) return fail(ctx, FRI_EINVAL, "degree buffer too small (n_layers entries)");
-    for (uint32_t k = 0; k < n; k++) out[k] = h->deg[k];
-    return FRI_OK;
-}
-
-// fri_decommit_query on the member's slices (its layout is the plan's).
-extern "C" int fri_batch_decommit_query(fri_ctx* ctx, uint32_t member, uint64_t index, uint32_t* values,
-                                        size_t values_cap, uint8_t* paths, size_t paths_cap, size_t* paths_len) {
-    if (!ctx || !values || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
-    const DevState* h;
-    int rc = batch_member(ctx, member, &h);
-    if (rc) return rc;
-    const Batch& B = ctx->batch;
-    if (h->n_layers == 0) return fail(ctx, FRI_ESTATE, "no committed layers of this member");
-    DecommitPlan dp{};
-    dp.index = index;
-    dp.log_n = B.log_n;
-    dp.n_layers = h->n_layers;
-    uint32_t words = 0;
-    for (uint32_t k = 0; k < dp.n_layers; k++) {
-        dp.layer_off[k] = B.lay.layer_off[k];
-        dp.tree_off[k] = B.lay.tree_off[k];
-        dp.path_off[k] = words;
-        words += 16 * (B.log_n - k);
-    }
-    *paths_len = (size_t)words * 4;
-    if (values_cap < 2 * (size_t)dp.n_layers) return fail(ctx, FRI_EINVAL, "values buffer too small (2 per layer)");
-    if (!paths || paths_cap < (size_t)words * 4) return fail(ctx, FRI_EINVAL, "paths buffer too small (see paths_len)");
-    if ((2 * (size_t)dp.n_layers + words) * 4 > 65536) return fail(ctx, FRI_EINVAL, "decommitment too large");
-    FRI_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = dq_alloc(ctx))) return rc;
-    launch_decommit_gather(B.b.words(BB_LAYERS) + member * B.lay_stride, B.b.words(BB_TREES) + member * B.tre_stride, dp,
-                           ctx->dq_dev, ctx->stream);
-    FRI_HIP(ctx, hipGetLastError());
-    FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(values, ctx->dq_host, 2 * dp.n_layers * 4);
-    memcpy(paths, ctx->dq_host + 2 * dp.n_layers, (size_t)words * 4);
-    return FRI_OK;
-}
-
 // ------------------------------------------------------ batched prover ----
 // B proofs of one shape (log_t, log_blowup, offset): what fri_trace_commit,
 // fri_fibsq_composition_commit and the per-query read-backs do for one proof,
@@ -418,47 +313,14 @@ static int hq_grow(fri_ctx* ctx, size_t bytes) {
     return FRI_OK;
 }
 
-// The shape's checks and, with q, the composition kernel's constants of it.
-static int fibsq_shape(fri_ctx* ctx, uint32_t log_t, uint32_t log_blowup, uint32_t offset, uint32_t batch,
-                       FibsqParams* q) {
-    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
-    if (log_blowup < 1 || ((uint32_t)1 << log_blowup) > FIBSQ_MAX_B)
-        return fail(ctx, FRI_EINVAL, "log_blowup must be 1..4 (deg CP = T needs n > T)");
-    if (log_t < 2) return fail(ctx, FRI_EINVAL, "trace needs at least 4 rows");
-    if (log_t > FRI_BATCH_MAX_LOG_N || log_t + log_blowup > FRI_BATCH_MAX_LOG_N)
-        return fail(ctx, FRI_EINVAL, "log_t + log_blowup above FRI_BATCH_MAX_LOG_N");
-    const uint32_t L = log_t + log_blowup;
-    if (L > ctx->log_n_max) return fail(ctx, FRI_EINVAL, "log_t + log_blowup out of range for context");
-    if (offset == 0 || offset >= P) return fail(ctx, FRI_EINVAL, "offset must be a nonzero canonical element");
-    const size_t T = (size_t)1 << log_t;
-    const uint32_t Bl = 1u << log_blowup;
-    const uint32_t w = root_of_unity(L), g = root_of_unity(log_t), wB = root_of_unity(log_blowup);
-    const uint32_t offT = pow_std(offset, T);
-    uint32_t zinv[FIBSQ_MAX_B];
-    for (uint32_t j = 0; j < Bl; j++) {
-        const uint32_t z = sub(mul_std(offT, pow_std(wB, j)), 1u);
-        if (z == 0) return fail(ctx, FRI_EINVAL, "offset^T lies in <w_B>: the coset meets the trace domain");
-        zinv[j] = to_mont(inv_std(z));
-    }
-    if (!q) return FRI_OK;
-    *q = FibsqParams{};
-    q->log_n = L;
-    q->B = Bl;
-    q->offset_m = to_mont(offset);
-    q->w_m = to_mont(w);
-    q->winv_m = to_mont(inv_std(w));
-    q->glast_m = to_mont(pow_std(g, T - 1));
-    q->gprev_m = to_mont(pow_std(g, T - 2));
-    for (uint32_t j = 0; j < Bl; j++) q->zinv_m[j] = zinv[j];
-    return FRI_OK;
-}
-
 extern "C" int fri_trace_commit_batch(fri_ctx* ctx, const uint32_t* traces, uint32_t log_t, uint32_t log_blowup,
                                       uint32_t offset, uint32_t batch, uint8_t* roots32) {
     if (!ctx || !traces || !roots32) return fail(ctx, FRI_EINVAL, "null argument");
     int rc = batch_ctx_ok(ctx);
     if (rc) return rc;
-    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, batch, nullptr))) return rc;
+    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
+    FibsqParams q;                                   // (the checks are what the trace commit needs of it)
+    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, true, &q))) return rc;
     const uint32_t L = log_t + log_blowup;
     const size_t T = (size_t)1 << log_t, n = (size_t)1 << L;
     for (uint32_t b = 0; b < batch; b++)
@@ -519,7 +381,8 @@ extern "C" int fri_fibsq_composition_commit_batch(fri_ctx* ctx, uint32_t log_t, 
     if (flags & ~FRI_FLAG_NO_GRAPH)
         return fail(ctx, FRI_EINVAL, "fri_fibsq_composition_commit_batch takes FRI_FLAG_NO_GRAPH only");
     FibsqParams q;
-    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, batch, &q))) return rc;
+    if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
+    if ((rc = fibsq_shape(ctx, log_t, log_blowup, offset, true, &q))) return rc;
     for (uint32_t b = 0; b < batch; b++)
         if (a_last[b] >= P || alphas[3 * b] >= P || alphas[3 * b + 1] >= P || alphas[3 * b + 2] >= P)
             return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": a_last / alphas not canonical");

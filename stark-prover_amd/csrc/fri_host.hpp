@@ -9,13 +9,17 @@
 //   fri_multipoint.hip evaluation and interpolation at arbitrary points, on the tree
 //   fri_commit.hip     the commit plan (layout, allocation) and the 1-GPU
 //                      commit (static launch sequence, hipGraph capture/replay)
-//   fri_batch.hip      the batched commit of many small codewords, its
-//                      member-wise read-backs and the batched prover entry
-//                      points (trace commit, composition commit, query round)
+//   fri_batch.hip      the batched commit of many small codewords and the
+//                      batched prover entry points (trace commit, composition
+//                      commit, query round)
 //   fri_verify.hip     the batched verifier: staging, chunking, the launch pair
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
 //                      which commit the read-backs serve (residency)
-//   fri_readback.hip   read-backs, decommitment and the prover entry points
+//   fri_readback.hip   read-backs and decommitment of a committed proof, the
+//                      single commit's and member-wise (one set of bodies)
+//   fri_fibsq.hip      the single-proof prover entry points (trace commit,
+//                      FibonacciSq composition commit, trace decommitment) and
+//                      the FibonacciSq shape both composition commits share
 //   fri_transport.hip  collective transports (RCCL, host callbacks, loopback,
 //                      in-process peer) and their self-test
 //   fri_sharded.hip    one rank's coset-sharded commit and decommitment
@@ -523,19 +527,42 @@ inline uint32_t post_scale(uint32_t log_N, uint32_t r_pow) {
     for (uint32_t i = 0; i < r_pow; i++) scale = mul_std(scale, R_MOD_P);
     return scale;
 }
+// batch > 1: that many transforms in the same launches, transform b from
+// src + b * src_stride into dst + b * dst_stride (NttPlan, fri_internal.hpp).
 inline void inverse_with(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, const uint32_t* post_lo,
-                         const uint32_t* post_hi, uint32_t* dst) {
-    NttPlan p{};
-    p.log_n = log_N;
+                         const uint32_t* post_hi, uint32_t* dst, uint32_t batch = 0, size_t src_stride = 0,
+                         size_t dst_stride = 0) {
+    NttPlan p = lde_plan(ctx, log_N);
     p.tw = ctx->tw_inv;
     p.post_lo = post_lo;
     p.post_hi = post_hi;
+    p.batch = batch;
+    p.src_stride = src_stride;
+    p.dst_stride = dst_stride;
     launch_ntt(p, src, (size_t)1 << log_N, dst, ctx->stream);
+}
+// The coset iNTT: dst[j] = N^-1 * R^r_pow * base^j * iNTT(src)[j], the
+// coefficients of the polynomial whose values on base^-1 * <w_N> are src
+// (Polynomial::interpolate, ops.rs:239-241).  The post-scale table is made on
+// the stream, in ctx->pow_lo / pow_hi.
+inline void coset_inverse(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, uint32_t base, uint32_t r_pow,
+                          uint32_t* dst, uint32_t batch = 0, size_t src_stride = 0, size_t dst_stride = 0) {
+    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, base, post_scale(log_N, r_pow), ctx->stream);
+    inverse_with(ctx, src, log_N, ctx->pow_lo, ctx->pow_hi, dst, batch, src_stride, dst_stride);
 }
 // dst = N^-1 * R^r_pow * iNTT(src)
 inline void inverse(fri_ctx* ctx, const uint32_t* src, uint32_t log_N, uint32_t r_pow, uint32_t* dst) {
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, 1u, post_scale(log_N, r_pow), ctx->stream);
-    inverse_with(ctx, src, log_N, ctx->pow_lo, ctx->pow_hi, dst);
+    coset_inverse(ctx, src, log_N, 1u, r_pow, dst);
+}
+// The coset LDE: dst[i] = sum_{j<len} src[j] (offset * w_N^i)^j, the values on
+// offset * <w_N> (fri_commit.rs:78); the pre-scale table as coset_inverse's.
+inline void coset_forward(fri_ctx* ctx, const uint32_t* src, size_t len, uint32_t log_N, uint32_t offset,
+                          uint32_t* dst) {
+    NttPlan p = lde_plan(ctx, log_N);
+    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, offset, 1u, ctx->stream);
+    p.pre_lo = ctx->pow_lo;
+    p.pre_hi = ctx->pow_hi;
+    launch_ntt(p, src, len, dst, ctx->stream);
 }
 // Power-series inverse g = F^-1 mod x^K by Newton's iteration
 //   g <- g (2 - F g) mod x^m2,  m -> m2 = min(2m, K),
@@ -622,9 +649,34 @@ int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* 
                               uint32_t* coeffs_out, size_t* len_out);
 
 // ---- fri_readback.hip
+// One committed proof as the read-backs see it: the single commit (its lane's
+// plan) or one member of the resident batch (its slices of Batch's buffers).
+struct ProofView {
+    const uint32_t* layers = nullptr;     // base of its layer slices
+    const uint32_t* trees = nullptr;      // ... and of its tree slices
+    const size_t* layer_off = nullptr;    // the layout's offsets (Plan::layer_off / tree_off)
+    const size_t* tree_off = nullptr;
+    uint32_t log_n = 0;
+    uint32_t n_layers = 0;                // layers it serves: none without a valid plan, or of a failed member
+    const DevState* st = nullptr;         // its copied-out state
+    bool member = false;                  // refusals say "... of this member"
+};
+ProofView single_view(fri_ctx* ctx);          // the resident single commit, its lane drained (settle)
+// The DecommitPlan of a whole query of v (index, shape, layer / tree / path
+// offsets) and *words, the path words it writes after its 2 values per layer;
+// *paths_len is set, then the buffers' capacities and the 64 KiB of the gather
+// output are checked.
+int decommit_plan(fri_ctx* ctx, const ProofView& v, uint64_t index, size_t values_cap, const uint8_t* paths,
+                  size_t paths_cap, size_t* paths_len, DecommitPlan* dp, uint32_t* words);
 int dq_alloc(fri_ctx* ctx);                   // pinned host buffer the gather kernels write
 // FRI_ESTATE of a single-commit read-back that finds no such layer
 int no_layer(fri_ctx* ctx, const char* what);
+
+// ---- fri_fibsq.hip
+// The FibonacciSq shape's checks and, in *q, the composition kernel's
+// constants of it (a_last and alpha_m are the caller's to fill).  batch_caps:
+// the batched prover's limits on top (FRI_BATCH_MAX_LOG_N, the context's size).
+int fibsq_shape(fri_ctx* ctx, uint32_t log_t, uint32_t log_blowup, uint32_t offset, bool batch_caps, FibsqParams* q);
 
 // ---- fri_batch.hip
 void batch_free(fri_ctx* ctx);                // fri_ctx_destroy

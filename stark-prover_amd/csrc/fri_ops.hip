@@ -34,11 +34,7 @@ extern "C" int fri_lde(fri_ctx* ctx, const uint32_t* coeffs, size_t d, uint32_t 
     if (!check_canonical(coeffs, d)) return fail(ctx, FRI_EINVAL, "coefficient not canonical (>= p)");
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     if (d) FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_a, coeffs, d * 4, hipMemcpyHostToDevice, ctx->stream));
-    NttPlan p = lde_plan(ctx, log_n);
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_n, offset, 1u, ctx->stream);
-    p.pre_lo = ctx->pow_lo;
-    p.pre_hi = ctx->pow_hi;
-    launch_ntt(p, ctx->scratch_a, d, ctx->scratch_b, ctx->stream);
+    coset_forward(ctx, ctx->scratch_a, d, log_n, offset, ctx->scratch_b);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(evals_out, ctx->scratch_b, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -54,20 +50,12 @@ extern "C" int fri_interpolate(fri_ctx* ctx, const uint32_t* ys, uint32_t log_n,
     if (!check_canonical(ys, n)) return fail(ctx, FRI_EINVAL, "value not canonical (>= p)");
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_a, ys, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    NttPlan p{};
-    p.log_n = log_n;
-    p.tw = ctx->tw_inv;
     // coeff_j = n^-1 * offset^-j * sum_i ys_i w^-ij
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_n, inv_std(offset), inv_std((uint32_t)(n % P)), ctx->stream);
-    p.post_lo = ctx->pow_lo;
-    p.post_hi = ctx->pow_hi;
-    launch_ntt(p, ctx->scratch_a, n, ctx->scratch_b, ctx->stream);
+    coset_inverse(ctx, ctx->scratch_a, log_n, inv_std(offset), 0, ctx->scratch_b);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(coeffs_out, ctx->scratch_b, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    size_t len = n;
-    while (len > 0 && coeffs_out[len - 1] == 0) len--;          // Polynomial::new trim (ops.rs:19-37)
-    *len_out = len;
+    *len_out = trimmed(coeffs_out, n);                           // Polynomial::new trim (ops.rs:19-37)
     return FRI_OK;
 }
 
@@ -82,7 +70,6 @@ int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* 
                               uint32_t* coeffs_out, size_t* len_out) {
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t N = (size_t)1 << log_N;
     int rc = ensure_tmp(ctx, interp_tmp_words(n, log_N));
     if (rc) return rc;
     FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_a, xs, n * 4, hipMemcpyHostToDevice, s));
@@ -91,13 +78,7 @@ int interpolate_points_direct(fri_ctx* ctx, const uint32_t* xs, const uint32_t* 
     FRI_HIP(ctx, hipMemcpyAsync(ctx->scratch_b, ys, n * 4, hipMemcpyHostToDevice, s));   // after the inverse (stream order)
     launch_interp_coeffs(ctx->scratch_b, ctx->scratch_c, n, s);             // c_j = y_j w_j
     launch_interp_eval(ctx->scratch_a, ctx->scratch_c, n, log_N, ctx->scratch_b, ctx->interp_tmp, s);   // f(w_N^k)
-    NttPlan p{};
-    p.log_n = log_N;
-    p.tw = ctx->tw_inv;
-    launch_pow_table(ctx->pow_lo, ctx->pow_hi, log_N, 1u, inv_std((uint32_t)(N % P)), s);   // N^-1
-    p.post_lo = ctx->pow_lo;
-    p.post_hi = ctx->pow_hi;
-    launch_ntt(p, ctx->scratch_b, N, ctx->scratch_a, s);
+    inverse(ctx, ctx->scratch_b, log_N, 0, ctx->scratch_a);
     FRI_HIP(ctx, hipGetLastError());
     FRI_HIP(ctx, hipMemcpyAsync(coeffs_out, ctx->scratch_a, n * 4, hipMemcpyDeviceToHost, s));   // deg f < n
     FRI_HIP(ctx, hipStreamSynchronize(s));
@@ -171,8 +152,7 @@ extern "C" int fri_merkle_root(fri_ctx* ctx, const uint32_t* values, size_t n, u
     uint32_t* tree = nullptr;
     bool pow2 = (n & (n - 1)) == 0;
     if (pow2) {
-        uint32_t L = 0;
-        while (((size_t)1 << L) < n) L++;
+        const uint32_t L = ceil_log2(n);
         const int rc = ensure_tmp(ctx, ((size_t)2 << L) * 8);
         if (rc) return rc;
         tree = ctx->interp_tmp;

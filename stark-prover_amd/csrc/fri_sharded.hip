@@ -369,47 +369,34 @@ extern "C" int fri_decommit_query_sharded(fri_ctx* ctx, uint64_t index, uint32_t
 int fri::decommit_sharded(fri_ctx* ctx, uint64_t index, uint32_t* values, size_t values_cap, uint8_t* paths,
                             size_t paths_cap, size_t* paths_len) {
     if (!ctx || !values || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
-    settle(ctx);
+    const ProofView v = single_view(ctx);
     const Plan& p = ctx->plan;
-    if (!p.valid || ctx->h_state->n_layers == 0) return fail(ctx, FRI_ESTATE, "no committed layers");
+    if (v.n_layers == 0) return fail(ctx, FRI_ESTATE, "no committed layers");
     if (!ctx->sharded_layers || !p.sharded) return fail(ctx, FRI_ESTATE, "last commit was not sharded: use fri_decommit_query");
     if (!ctx->tp.host && !ctx->tp.comm && !ctx->tp.loop && !ctx->tp.peer)
         return fail(ctx, FRI_ESTATE, "no transport attached (detached or aborted)");
     const uint32_t G = p.G;
     if ((uint32_t)ctx->tp.world != G) return fail(ctx, FRI_ESTATE, "transport world differs from the commit's");
-    uint32_t logG = 0;
-    while ((1u << logG) < G) logG++;
-    DecommitPlan dp{};
-    dp.index = index;
-    dp.log_n = p.log_n;
-    dp.n_layers = ctx->h_state->n_layers;
+    DecommitPlan dp;
+    uint32_t words;
+    int rc = decommit_plan(ctx, v, index, values_cap, paths, paths_cap, paths_len, &dp, &words);
+    if (rc) return rc;
+    const uint32_t logG = ceil_log2(G);
     dp.logG = logG;
     const bool local_tail = p.k_sw < p.rmax;
-    uint32_t words = 0;
-    for (uint32_t k = 0; k < dp.n_layers; k++) {
-        dp.layer_off[k] = p.layer_off[k];
-        dp.tree_off[k] = p.tree_off[k];
-        dp.path_off[k] = words;
-        words += 16 * (p.log_n - k);
-        if (k < ctx->sharded_layers) {
-            dp.shard_lb1[k] = (uint8_t)(p.log_n - k - logG + 1);
-            dp.val_block[k] = ((int)k == p.k_sw && local_tail) ? 0 : 1;   // the switch layer's slot was gathered whole
-            dp.owned[k] = (uint64_t)1 << p.block[k];
-            dp.top_off[k] = (uint64_t)k * 2 * 64 * 8;
-        }
+    for (uint32_t k = 0; k < ctx->sharded_layers && k < dp.n_layers; k++) {
+        dp.shard_lb1[k] = (uint8_t)(p.log_n - k - logG + 1);
+        dp.val_block[k] = ((int)k == p.k_sw && local_tail) ? 0 : 1;   // the switch layer's slot was gathered whole
+        dp.owned[k] = (uint64_t)1 << p.block[k];
+        dp.top_off[k] = (uint64_t)k * 2 * 64 * 8;
     }
-    *paths_len = (size_t)words * 4;
-    if (values_cap < 2 * (size_t)dp.n_layers) return fail(ctx, FRI_EINVAL, "values buffer too small (2 per layer)");
-    if (!paths || paths_cap < (size_t)words * 4) return fail(ctx, FRI_EINVAL, "paths buffer too small (see paths_len)");
     const size_t tw = 2 * (size_t)dp.n_layers + words;
-    if (tw * 4 > 65536) return fail(ctx, FRI_EINVAL, "decommitment too large");
     FRI_HIP(ctx, hipSetDevice(ctx->device));
     DistBuf& db = ctx->db;
     constexpr size_t SLOT = 16384;                          // words per rank slot (64 KiB)
     if (!db.dq) FRI_HIP(ctx, dalloc(ctx, &db.dq, (size_t)(64 + 1) * SLOT * 4));
     ctx->tp.log.clear();
-    int rc = tp_host_stage(ctx, G * SLOT * 4);
-    if (rc) return rc;
+    if ((rc = tp_host_stage(ctx, G * SLOT * 4))) return rc;
     hipStream_t s = ctx->stream;
     launch_decommit_gather(p.layers, p.trees, dp, db.dq, s, db.top);
     FRI_HIP(ctx, hipGetLastError());

@@ -242,6 +242,31 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
 
 
+def _openings(values, raw: bytes, n_layers: int, log_n: int, first_value: int = 0, first_byte: int = 0):
+    """decommit_query's tuples out of a gather record: layer k's two values from
+    values[first_value + 2k:], its two paths of 32 (log_n - k) bytes after the earlier layers' from raw[first_byte:]."""
+    out, off, v = [], first_byte, first_value
+    for k in range(n_layers):
+        pl = 32 * (log_n - k)
+        out.append((int(values[v + 2 * k]), int(values[v + 2 * k + 1]), raw[off:off + pl], raw[off + pl:off + 2 * pl]))
+        off += 2 * pl
+    return out
+
+
+def _digests(raw: bytes) -> List[bytes]:
+    return [raw[i:i + 32] for i in range(0, len(raw), 32)]
+
+
+def _check_resident(generation: Optional[int], log_n: int, g: int, ln: int, present, what: str) -> None:
+    """Read-backs serve only the commit they were asked for: the resident
+    codeword (if ``present``) must be 2^log_n and, for a FRIProof, still the
+    commit of ``generation`` (a later commit on this context replaced its layers)."""
+    if generation is not None and g != generation:
+        raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
+    if present and ln != log_n:
+        raise FriError(FRI_ESTATE, f"resident {what} is 2^{ln}, not 2^{log_n}")
+
+
 class Context:
     """Owns one fri_ctx (device buffers, stream, graphs) on one GPU, or, from
     ``Context.multi``, a team of ranks on several GPUs behind one context."""
@@ -600,8 +625,7 @@ class Context:
         cnt = 1 << (log_n - k - level)
         buf = ctypes.create_string_buffer(32 * cnt)
         self._check(self.lib.fri_batch_tree_level_copy(self.h, member, k, level, buf, 32 * cnt))
-        raw = buf.raw
-        return [raw[32 * i: 32 * i + 32] for i in range(cnt)]
+        return _digests(buf.raw)
 
     def batch_commit_degrees(self, member: int) -> List[int]:
         out = (ctypes.c_int32 * (MAX_ROUNDS + 1))()
@@ -617,12 +641,7 @@ class Context:
         ln = ctypes.c_size_t()
         self._check(self.lib.fri_batch_decommit_query(self.h, member, index, _ptr(vals), vals.size, buf, total,
                                                       ctypes.byref(ln)))
-        out, off = [], 0
-        for k in range(n_layers):
-            pl = 32 * (log_n - k)
-            out.append((int(vals[2 * k]), int(vals[2 * k + 1]), buf.raw[off:off + pl], buf.raw[off + pl:off + 2 * pl]))
-            off += 2 * pl
-        return out
+        return _openings(vals, buf.raw, n_layers, log_n)
 
     # ---- batched prover ----------------------------------------------------
     def trace_commit_batch(self, traces, log_blowup: int, offset: int = GENERATOR) -> List[bytes]:
@@ -741,14 +760,8 @@ class Context:
         return g.value, ln.value, nl.value
 
     def _resident(self, log_n: int, generation: Optional[int] = None) -> None:
-        """Read-backs serve only the commit they were asked for: the resident
-        codeword must be 2^log_n and, for a FRIProof, still the commit of
-        ``generation`` (a later commit on this context replaced its layers)."""
         g, ln, nl = self.commit_info()
-        if generation is not None and g != generation:
-            raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
-        if nl and ln != log_n:
-            raise FriError(FRI_ESTATE, f"resident commit is 2^{ln}, not 2^{log_n}")
+        _check_resident(generation, log_n, g, ln, nl, "commit")
 
     def layer(self, k: int, log_n: int, generation: Optional[int] = None) -> np.ndarray:
         self._resident(log_n, generation)
@@ -761,8 +774,7 @@ class Context:
         cnt = 1 << (log_n - k - level)
         buf = ctypes.create_string_buffer(32 * cnt)
         self._check(self.lib.fri_tree_level_copy(self.h, k, level, buf, 32 * cnt))
-        raw = buf.raw
-        return [raw[32 * i: 32 * i + 32] for i in range(cnt)]
+        return _digests(buf.raw)
 
     def auth_path(self, k: int, index: int, log_n: int):
         self._resident(log_n)
@@ -771,7 +783,7 @@ class Context:
         val = ctypes.c_uint32()
         dep = ctypes.c_uint32()
         self._check(self.lib.fri_auth_path(self.h, k, index, ctypes.byref(val), buf, ctypes.byref(dep)))
-        return val.value, [buf.raw[32 * i: 32 * i + 32] for i in range(dep.value)]
+        return val.value, _digests(buf.raw[:32 * dep.value])
 
     def trace_commit(self, trace, log_blowup: int, offset: int = GENERATOR, readback: bool = True):
         """fri_trace_commit: (LDE Merkle root bytes, trimmed trace-polynomial
@@ -835,12 +847,7 @@ class Context:
         ln = ctypes.c_size_t()
         fn = self.lib.fri_decommit_query_sharded if sharded else self.lib.fri_decommit_query
         self._check(fn(self.h, index, _ptr(vals), vals.size, buf, total, ctypes.byref(ln)))
-        out, off = [], 0
-        for k in range(n_layers):
-            pl = 32 * (log_n - k)
-            out.append((int(vals[2 * k]), int(vals[2 * k + 1]), buf.raw[off:off + pl], buf.raw[off + pl:off + 2 * pl]))
-            off += 2 * pl
-        return out
+        return _openings(vals, buf.raw, n_layers, log_n)
 
     # ---- multi-GPU ---------------------------------------------------------
     @staticmethod
@@ -1157,10 +1164,7 @@ class BatchMember:
 
     def _resident(self, log_n: int, generation: Optional[int] = None) -> None:
         g, b, ln = self.ctx.batch_info()
-        if generation is not None and g != generation:
-            raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
-        if b and ln != log_n:
-            raise FriError(FRI_ESTATE, f"resident batch is 2^{ln}, not 2^{log_n}")
+        _check_resident(generation, log_n, g, ln, b, "batch")
 
     def commit_degrees(self) -> List[int]:
         return self.ctx.batch_commit_degrees(self.member)
@@ -1186,7 +1190,7 @@ class BatchMember:
         if not 0 <= index < (1 << (log_n - k)):
             raise FriError(FRI_EINVAL, "index out of range")
         val, _, path, _ = self.ctx.batch_decommit_query(self.member, index, len(self.commit_degrees()), log_n)[k]
-        return val, [path[32 * i: 32 * i + 32] for i in range(log_n - k)]
+        return val, _digests(path)
 
 
 @dataclass
@@ -1722,13 +1726,7 @@ def batch_round_records(values: np.ndarray, paths: np.ndarray, paths_len: int, t
         raise FriError(FRI_ESTATE, "the record does not hold this many layers (a skipped or failed member?)")
     raw = paths[:paths_len].tobytes()
     trace = [(int(values[j]), raw[j * tl:(j + 1) * tl]) for j in range(trace_count)]
-    off, openings = trace_count * tl, []
-    for k in range(n_layers):
-        pl = 32 * (log_n - k)
-        openings.append((int(values[trace_count + 2 * k]), int(values[trace_count + 2 * k + 1]), raw[off:off + pl],
-                         raw[off + pl:off + 2 * pl]))
-        off += 2 * pl
-    return trace, openings
+    return trace, _openings(values, raw, n_layers, log_n, trace_count, trace_count * tl)
 
 
 def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIProof"],

@@ -74,6 +74,32 @@ def test_empty_list_touches_no_device():
         fri_amd.fri_commit_batch([[1, 2]], 10, [])       # one channel per polynomial
 
 
+def test_openings_are_taken_apart_per_layer():
+    """_openings (behind decommit_query, batch_decommit_query and
+    batch_round_records) on a hand-built record of log_n = 3, n_layers = 2:
+    three trace values and five trace-path bytes come first."""
+    values = np.array([91, 92, 93, 10, 11, 20, 21], dtype=np.uint32)
+    p0, s0, p1, s1 = bytes([1]) * 96, bytes([2]) * 96, bytes([3]) * 64, bytes([4]) * 64
+    raw = b"trace" + p0 + s0 + p1 + s1
+    assert fri_amd._openings(values, raw, 2, 3, 3, 5) == [(10, 11, p0, s0), (20, 21, p1, s1)]
+    assert fri_amd._openings(values[3:], raw[5:], 2, 3) == [(10, 11, p0, s0), (20, 21, p1, s1)]
+    assert fri_amd._openings(values, raw, 1, 3, 3, 5) == [(10, 11, p0, s0)]
+    got = fri_amd._openings(values, raw, 2, 3, 3, 5)
+    assert all(type(v) is int for t in got for v in t[:2]) and all(type(b) is bytes for t in got for b in t[2:])
+    # a 1-element last layer has empty paths: log_n = 1 folded once
+    a, b = bytes([7]) * 32, bytes([8]) * 32
+    assert fri_amd._openings([5, 6, 9, 9], a + b, 2, 1) == [(5, 6, a, b), (9, 9, b"", b"")]
+    assert fri_amd._openings([5, 6, 9, 9], a + b, 0, 1) == []
+    # batch_round_records goes through it: one trace opening, then the two layers
+    tl = 96
+    paths = np.frombuffer(bytes([9]) * tl + p0 + s0 + p1 + s1 + b"junk", dtype=np.uint8)
+    trace, openings = fri_amd.batch_round_records(values[2:], paths, tl + 320, 1, 2, 3)
+    assert trace == [(93, bytes([9]) * tl)] and openings == [(10, 11, p0, s0), (20, 21, p1, s1)]
+    with pytest.raises(fri_amd.FriError):
+        fri_amd.batch_round_records(values[2:], paths, tl + 320, 1, 1, 3)     # the record holds two layers
+    assert fri_amd._digests(a + b) == [a, b] and fri_amd._digests(b"") == []
+
+
 class StubContext:
     """What fri_commit_batch and BatchMember call of a Context, recorded."""
     n_ranks = 1

@@ -81,6 +81,39 @@ def test_composition_detects_constraint_violation(ctx):
     assert res.n_rounds == log_t + 1
 
 
+def test_composition_commit_refuses_bad_shapes(ctx, golden):
+    """fri_fibsq_composition_commit's shape refusals, each behind a resident
+    trace commit of that very shape (so it is the shape check that refuses),
+    then a golden proof on the same context."""
+    import fri_amd
+
+    def refused(log_t, lb, offset=fri_amd.GENERATOR, a_last=None, alphas=(1, 2, 3), flags=0):
+        trace = fri_amd.fibsq_trace(7, 1 << log_t)
+        ctx.trace_commit(trace, lb, offset=offset, readback=False)
+        al = np.array(alphas, dtype=np.uint32)
+        ch, res = fri_amd.ChannelState(), fri_amd.CommitResult()
+        a_last = int(trace[-1]) if a_last is None else a_last
+        return ctx.lib.fri_fibsq_composition_commit(ctx.h, log_t, lb, offset, a_last, fri_amd._ptr(al), ctypes.byref(ch),
+                                                    flags, ctypes.byref(res))
+
+    E = fri_amd.FRI_EINVAL
+    assert refused(4, 0) == E                              # log_blowup below 1
+    assert refused(4, 5) == E                              # ... above 4
+    assert refused(1, 1) == E                              # fewer than 4 rows
+    assert refused(4, 3, offset=1) == E                    # 1^T lies in <w_B>
+    for j in range(3):
+        assert refused(4, 3, alphas=[P if i == j else i + 1 for i in range(3)]) == E
+    assert refused(4, 3, a_last=P) == E
+    assert refused(4, 3, flags=fri_amd.FLAG_FORCE_BETAS) == E
+    assert refused(4, 3) == fri_amd.FRI_OK                 # the helper's call is a good one otherwise
+    c = golden["fibsq"][2]
+    ch = fri_amd.Channel(state=c["channel_in"])
+    pr = fri_amd.prove_fibsq(c["a1"], c["log_t"], c["log_blowup"], c["queries"], ch, ctx=ctx)
+    assert pr.trace_root.hex() == c["trace_root"] and [r.hex() for r in pr.fri.roots] == c["roots"]
+    assert ch.state == c["channel_out"]
+    assert len(ch.proof) == c["messages"] and _proof_sha(ch.proof) == c["proof_sha256"]
+
+
 def test_prover_entry_errors(ctx):
     import fri_amd
     trace = fri_amd.fibsq_trace(7, 1 << 8)
