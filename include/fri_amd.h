@@ -595,6 +595,64 @@ int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* 
                           uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
                           size_t paths_stride, size_t* paths_len);
 
+/* fri_batch_query_phase: the WHOLE query phase of every member of the resident
+ * batch in one call, the members' channels included.
+ * For every served member b it is num_queries x { receive_random_int(0,
+ * max_index, true); the sends of prove_fibsq's query round } on chan[b]; with
+ * trace_count = 0 the sends are decommit_fri_layers' alone.  The message order
+ * is the one fri_verify_batch replays, the doubled value of a one-element
+ * layer included.
+ *   chan[b]: in, the channel before the first draw; out, after the last send.
+ *   indices[b*num_queries + q]: the index drawn for member b's query q.
+ *   values + (b*num_queries + q)*values_stride, paths + (b*num_queries +
+ *     q)*paths_stride: fri_batch_query_round's record for that index, in the
+ *     layout fri_verify_batch takes (the outputs feed it without repacking).
+ *   paths_len[b]: the bytes of ONE query's paths of member b; 0 for a member
+ *     left out (skip[b] != 0, or its commit failed), whose chan[b], indices
+ *     and records are not touched.
+ * skip, trace_count and trace_stride are fri_batch_query_round's.
+ * num_queries = 0 returns FRI_OK with nothing written.
+ *
+ * With nothing written: FRI_ESTATE without a resident batch, or without the
+ * resident trace batch behind it when trace_count > 0, and on a profiling
+ * context; FRI_EINVAL for trace_count > 8, max_index >= 2^32, max_index >=
+ * 2^L with trace_count > 0, num_queries above FRI_VERIFY_MAX_QUERIES, a served
+ * member with has_state = 0 (the reference panics there, channel.rs:65), a
+ * multi-GPU context, and strides too small (the needed paths_stride in
+ * paths_len[0], as the round).
+ *
+ * How it runs: one lane per member draws each index, rehashes, and absorbs the
+ * openings in the transcript's order, reading values and sibling digests
+ * where they live, in the resident LDEs, layers and trees; a second kernel
+ * then gathers the records of the drawn indices, and one read-back brings
+ * indices, records and final states to the host.  The members go through
+ * device and pinned staging in chunks of a 256 MiB budget
+ * (fri_debug_set_query_chunk: members per chunk, 0 = by the budget).  The call
+ * reads and changes nothing of the resident batch: the commit generation does
+ * not move and fri_batch_query_round serves the same batch afterwards.
+ * FRI_ENOMEM leaves the context usable and what was resident readable.
+ *
+ * Measured (tools/batch_probe.py --prove, profiles/prove_batch_device_queries.txt,
+ * DESIGN.md section 4f; us per proof, blowup 8, the whole call of the Python
+ * mirror, round route -> this route): at log_t 7 with 32 queries 1338 -> 2638 at
+ * B = 16, 1213 -> 856 at 64, 1180 -> 478 at 256 and 1270 -> 423 at 4096; at
+ * log_t 13 with 32 queries 3009 -> 5512, 2317 -> 1861, 2121 -> 931 and 2212 ->
+ * 867.  One lane hashes a member's whole phase, so the chain kernel runs for
+ * milliseconds whatever the batch: at every measured shape (log_t 7, 10, 13 with
+ * 8 and 32 queries) the whole call is slower than the round route at B = 16
+ * (0.47x to 0.71x) and faster from B = 64, the smallest measured size where it
+ * wins, in both runs (1.1x to 1.5x at 64, 1.9x to 2.5x at 256, 2.4x to 3.0x at
+ * 4096).  The route is opt-in: no default uses it. */
+int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_t max_index,
+                          fri_channel_state* chan,          /* [batch] in: before the first draw; out: after the last send */
+                          const uint8_t* skip,              /* may be NULL, as fri_batch_query_round */
+                          uint32_t trace_count, uint64_t trace_stride,
+                          uint64_t* indices,                /* [batch][num_queries] out */
+                          uint32_t* values, size_t values_stride,   /* words per (member, query) */
+                          uint8_t* paths, size_t paths_stride,      /* bytes per (member, query) */
+                          size_t* paths_len);               /* [batch]: bytes per query of member b, 0 = left out */
+int fri_debug_set_query_chunk(fri_ctx* ctx, uint32_t members);     /* 0 = automatic */
+
 /* Batched verifier: `batch` transcripts of one shape checked in one call, the
  * counterpart of the batched prover.  verify_fri / verify_fibsq of the host
  * mirrors (one transcript, SHA-256 on one CPU core) stay the yardstick: for

@@ -504,3 +504,171 @@ extern "C" int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, cons
     ctx->err.clear();
     return FRI_OK;
 }
+
+// ------------------------------------------------ the query phase (device) ----
+// fri_batch_query_phase: all the queries of every member, the channels' draws
+// and sends included, in chunks of members under a staging budget; per chunk
+// one upload, k_query_chain, k_batch_query_all and one read-back on the
+// context stream.  Reads and changes nothing of the resident batch.
+namespace {
+constexpr size_t QUERY_CHUNK_BYTES = (size_t)256 << 20;   // device and pinned staging of one chunk
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// Sections of a chunk's staging for m members: the first three in BB_QMETA, the
+// records in BB_QOUT; the pinned buffer holds all four, the records last.
+struct QuerySections {
+    size_t chan, nl, idx, meta, rec, total;
+    QuerySections(size_t m, size_t q, size_t rec_words) {
+        size_t o = 0;
+        chan = o; o += al256(m * sizeof(fri_channel_state));
+        nl = o;   o += al256(m * 4);
+        idx = o;  o += al256(m * q * 8);
+        meta = o;
+        rec = m * q * rec_words * 4;
+        total = meta + rec;
+    }
+};
+}  // namespace
+
+extern "C" int fri_debug_set_query_chunk(fri_ctx* ctx, uint32_t members) {
+    if (!ctx) return FRI_EINVAL;
+    ctx->batch.query_chunk = members;
+    return FRI_OK;
+}
+
+extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_t max_index, fri_channel_state* chan,
+                                     const uint8_t* skip, uint32_t trace_count, uint64_t trace_stride,
+                                     uint64_t* indices, uint32_t* values, size_t values_stride, uint8_t* paths,
+                                     size_t paths_stride, size_t* paths_len) {
+    static_assert(sizeof(fri_channel_state) == 36, "k_query_chain reads a channel state as 9 words");
+    if (!ctx || !chan || !paths_len || (num_queries && (!indices || !values || !paths)))
+        return fail(ctx, FRI_EINVAL, "null argument");
+    int rc = batch_ctx_ok(ctx);
+    if (rc) return rc;
+    Batch& B = ctx->batch;
+    if (!B.resident)
+        return fail(ctx, FRI_ESTATE,
+                    "no resident batch: fri_batch_* serve the last fri_commit_batch until the next commit");
+    if (trace_count > 8) return fail(ctx, FRI_EINVAL, "trace_count must be 0..8");
+    const uint32_t L = B.log_n, batch = B.count, Q = num_queries;
+    if (trace_count && (!B.trace_resident || B.trace_count != batch || B.trace_log_t + B.trace_log_b != L))
+        return fail(ctx, FRI_ESTATE, "no resident trace batch behind this batch (fri_trace_commit_batch)");
+    if (max_index >> 32) return fail(ctx, FRI_EINVAL, "max_index must be below 2^32");
+    // (the FRI openings take any index, mod the layer's size; the trace's do not)
+    if (trace_count && (max_index >> L)) return fail(ctx, FRI_EINVAL, "max_index must be below 2^log_n with trace_count > 0");
+    if (Q > FRI_VERIFY_MAX_QUERIES) return fail(ctx, FRI_EINVAL, "num_queries above FRI_VERIFY_MAX_QUERIES");
+    if (Q == 0) {
+        ctx->err.clear();
+        return FRI_OK;
+    }
+    // who is served, and the record's shape
+    auto layers_of = [&](uint32_t b) { return (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers; };
+    uint32_t max_layers = 0, served = 0;
+    for (uint32_t b = 0; b < batch; b++) {
+        const uint32_t nl = layers_of(b);
+        if (!nl) continue;
+        if (!chan[b].has_state)
+            return fail(ctx, FRI_EINVAL,
+                        "member " + std::to_string(b) + ": an empty channel state draws no index (channel.rs:65)");
+        max_layers = std::max(max_layers, nl);
+        served++;
+    }
+    auto fri_path_words = [&](uint32_t nl) { return 16 * ((size_t)nl * L - (size_t)nl * (nl ? nl - 1 : 0) / 2); };
+    const size_t tpath_words = (size_t)trace_count * 8 * L;
+    const size_t val_words = trace_count + 2 * (size_t)max_layers;
+    const size_t rec_words = val_words + tpath_words + fri_path_words(max_layers);
+    if (served && (values_stride < val_words || paths_stride < (tpath_words + fri_path_words(max_layers)) * 4)) {
+        paths_len[0] = (tpath_words + fri_path_words(max_layers)) * 4;
+        return fail(ctx, FRI_EINVAL,
+                    "record strides too small (values: trace_count + 2 per layer words; paths: see paths_len[0])");
+    }
+    FRI_HIP(ctx, hipSetDevice(ctx->device));
+    // members per chunk: what the byte budget holds, or the hook's count; halved while the staging does not fit
+    size_t chunk = B.query_chunk ? B.query_chunk
+                                 : std::max<size_t>(QUERY_CHUNK_BYTES / QuerySections(1, Q, rec_words).total, 1);
+    chunk = std::min<size_t>(chunk, batch);
+    if (served)
+        for (;;) {
+            const QuerySections S(chunk, Q, rec_words);
+            size_t want[BB_N] = {};
+            want[BB_QMETA] = S.meta;
+            want[BB_QOUT] = S.rec;
+            rc = hq_grow(ctx, S.total);
+            if (!rc) rc = bufs_grow(ctx, B.b, want, 0);
+            if (!rc) break;
+            if (rc != FRI_ENOMEM || B.query_chunk || chunk == 1) return rc;
+            chunk = (chunk + 1) / 2;
+        }
+    for (uint32_t b = 0; b < batch; b++) paths_len[b] = 0;
+    if (!served) {
+        ctx->err.clear();
+        return FRI_OK;
+    }
+
+    QueryPhase qp{};
+    qp.layers = B.b.words(BB_LAYERS);
+    qp.trees = B.b.words(BB_TREES);
+    qp.lay_stride = B.lay_stride;
+    qp.tre_stride = B.tre_stride;
+    qp.tlde = B.b.words(BB_TLDE);
+    qp.ttree = B.b.words(BB_TTREE);
+    qp.tlde_stride = B.tlde_stride;
+    qp.ttree_stride = B.ttree_stride;
+    qp.rec_words = rec_words;
+    qp.trace_stride = trace_stride;
+    qp.range = max_index + 1;
+    qp.num_queries = Q;
+    qp.log_n = L;
+    qp.trace_count = trace_count;
+    qp.max_layers = max_layers;
+    for (int k = 0; k <= B.lay.rmax + 1; k++) {
+        qp.layer_off[k] = (uint32_t)B.lay.layer_off[k];
+        qp.tree_off[k] = (uint32_t)B.lay.tree_off[k];
+    }
+    hipStream_t s = ctx->stream;
+    uint8_t* dmeta = static_cast<uint8_t*>(B.b.dev[BB_QMETA]);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t m = std::min<size_t>(chunk, batch - b0);
+        const QuerySections S(m, Q, rec_words);
+        fri_channel_state* hchan = reinterpret_cast<fri_channel_state*>(B.h_q + S.chan);
+        uint32_t* hnl = reinterpret_cast<uint32_t*>(B.h_q + S.nl);
+        const uint64_t* hidx = reinterpret_cast<const uint64_t*>(B.h_q + S.idx);
+        const uint32_t* hrec = reinterpret_cast<const uint32_t*>(B.h_q + S.meta);
+        bool any = false;
+        for (size_t i = 0; i < m; i++) {
+            hchan[i] = chan[b0 + i];
+            hnl[i] = layers_of((uint32_t)(b0 + i));
+            any = any || hnl[i];
+        }
+        if (!any) continue;
+        FRI_HIP(ctx, hipMemcpyAsync(dmeta, B.h_q, S.idx, hipMemcpyHostToDevice, s));     // the states and n_layers
+        qp.n_layers = reinterpret_cast<const uint32_t*>(dmeta + S.nl);
+        qp.chan = reinterpret_cast<uint32_t*>(dmeta + S.chan);
+        qp.indices = reinterpret_cast<uint64_t*>(dmeta + S.idx);
+        qp.out = B.b.words(BB_QOUT);
+        qp.first = (uint32_t)b0;
+        qp.members = (uint32_t)m;
+        launch_query_phase(qp, s);
+        FRI_HIP(ctx, hipGetLastError());
+        FRI_HIP(ctx, hipMemcpyAsync(B.h_q, dmeta, S.meta, hipMemcpyDeviceToHost, s));
+        FRI_HIP(ctx, hipMemcpyAsync(B.h_q + S.meta, qp.out, S.rec, hipMemcpyDeviceToHost, s));
+        // the next chunk reuses the staging
+        FRI_HIP(ctx, hipStreamSynchronize(s));
+        for (size_t i = 0; i < m; i++) {
+            const uint32_t nl = hnl[i];
+            if (!nl) continue;
+            const size_t b = b0 + i;
+            chan[b] = hchan[i];
+            for (size_t qi = 0; qi < Q; qi++) {
+                const uint32_t* rec = hrec + (i * Q + qi) * rec_words;
+                uint32_t* v = values + (b * Q + qi) * values_stride;
+                uint8_t* p = paths + (b * Q + qi) * paths_stride;
+                indices[b * Q + qi] = hidx[i * Q + qi];
+                memcpy(v, rec, (trace_count + 2 * (size_t)nl) * 4);
+                memcpy(p, rec + val_words, (tpath_words + fri_path_words(nl)) * 4);
+            }
+            paths_len[b] = (tpath_words + fri_path_words(nl)) * 4;
+        }
+    }
+    ctx->err.clear();
+    return FRI_OK;
+}

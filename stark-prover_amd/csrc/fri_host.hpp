@@ -163,6 +163,7 @@ struct Batch {
     // pinned staging of the query rounds and the trace roots (grown on demand)
     uint8_t* h_q = nullptr;
     size_t h_q_cap = 0;
+    uint32_t query_chunk = 0;    // fri_debug_set_query_chunk: members per chunk of fri_batch_query_phase (0: by byte budget)
 };
 
 // The batched verifier (fri_verify_batch, fri_verify.hip): one device buffer

@@ -360,6 +360,30 @@ struct BatchQuery {
     uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2];
 };
 void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s);
+// The whole query phase of `members` members of the resident batch, from member
+// `first` on (fri_batch_query_phase): k_query_chain draws every index from the
+// member's channel and absorbs the openings from the resident buffers, then
+// k_batch_query_all gathers the records, both on `s`.  The per-member arrays
+// are the chunk's (member first + m at m); n_layers[m] = 0 leaves a member out.
+struct QueryPhase {
+    const uint32_t* layers;      // the resident batch, as BatchQuery
+    const uint32_t* trees;
+    size_t lay_stride, tre_stride;
+    const uint32_t* tlde;
+    const uint32_t* ttree;
+    size_t tlde_stride, ttree_stride;
+    const uint32_t* n_layers;    // [members]
+    uint32_t* chan;              // [members] fri_channel_state, 9 words: in, and out after the last send
+    uint64_t* indices;           // [members][num_queries] out
+    uint32_t* out;               // [members][num_queries] records of rec_words words (k_batch_query's)
+    size_t rec_words;
+    uint64_t trace_stride;
+    uint64_t range;              // max_index + 1, <= 2^32
+    uint32_t first, members, num_queries;
+    uint32_t log_n, trace_count, max_layers;
+    uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2];
+};
+void launch_query_phase(const QueryPhase& q, hipStream_t s);
 
 // fri_verify_kernels.hip — the batched verifier (fri_verify_batch): `members`
 // transcripts of one shape, packed as fri_amd.h describes, in device memory

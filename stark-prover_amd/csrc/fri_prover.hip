@@ -16,6 +16,7 @@
 // The two per-point divisions share one batch inversion (Montgomery's trick
 // over CP_K consecutive points per lane, one Fermat inverse per lane).
 #include "fri_internal.hpp"
+#include "chan_send.hpp"
 
 namespace fri {
 
@@ -169,6 +170,133 @@ __global__ __launch_bounds__(64) void k_batch_query(BatchQuery q) {
 
 void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s) {
     hipLaunchKernelGGL(k_batch_query, dim3(q.trace_count + q.max_layers, batch), dim3(64), 0, s, q);
+}
+
+// ------------------------------------------------ the query phase (device) ---
+// fri_batch_query_phase: every query of every member of a batch, the members'
+// channels included.  The verifier's split, turned around:
+// k_query_chain runs each member's Fiat-Shamir chain and leaves the indices it
+// drew, then k_batch_query_all gathers the records of those indices.
+
+// One lane per member, workgroups of one wave (k_verify_chain's shape).  The
+// lane runs num_queries x { receive_random_int(0, range - 1, true), then the
+// sends of prove_fibsq's query round } in units of a few sends:
+//   0 the index, [1, 1 + tc) the trace openings (value, path), then per layer
+//   (value, path, sibling value, sibling path), a one-element layer's value
+//   once more first (fri_commit.rs:147-149).
+// Values and sibling digests are read where they live, in the member's trace
+// LDE and tree and its layers and trees (k_batch_query's addressing); nothing
+// is staged.  Every address is formed from the drawn index masked to the
+// layer's size.  Lanes past their member's last layer sit the unit out; a
+// member with n_layers = 0 is left out and nothing of it is written.
+__global__ __launch_bounds__(64) void k_query_chain(QueryPhase q) {
+    const uint32_t m = blockIdx.x * 64u + threadIdx.x;
+    if (m >= q.members) return;
+    const uint32_t nl = q.n_layers[m];
+    if (nl == 0) return;
+    const size_t b = (size_t)q.first + m;
+    const uint32_t L = q.log_n, ML = q.max_layers, tc = q.trace_count, Q = q.num_queries;
+    const uint32_t* lay = q.layers + b * q.lay_stride;
+    const uint32_t* tre = q.trees + b * q.tre_stride;
+    const uint32_t* tlde = q.tlde + b * q.tlde_stride;
+    const uint32_t* ttree = q.ttree + b * q.ttree_stride;
+    uint32_t* chan = q.chan + (size_t)m * 9u;
+    uint32_t cs[8], has;
+#pragma unroll
+    for (int j = 0; j < 8; j++) cs[j] = __builtin_bswap32(chan[j]);
+    has = chan[8] ? 1u : 0u;
+#pragma unroll 1
+    for (uint32_t qi = 0; qi < Q; qi++) {
+        uint64_t index = 0;
+        const uint32_t units = 1u + tc + ML;
+#pragma unroll 1
+        for (uint32_t u = 0; u < units; u++) {
+            const uint32_t nsub = u == 0 ? 1u : (u < 1u + tc ? 2u : (L - (u - 1u - tc) == 0u ? 5u : 4u));
+#pragma unroll 1
+            for (uint32_t s = 0; s < nsub; s++) {
+                uint32_t kind = MSG_PATH, nd = 0u, v = 0u;
+                TreeNodes src{tre, 0u, 0u};
+                bool act = true;
+                if (u == 0) {
+                    // the draw, then its rehash: send(b"") is sha256(hex(cs))
+                    index = chan_int(cs, q.range);
+                    q.indices[(size_t)m * Q + qi] = index;
+                } else if (u < 1u + tc) {
+                    const uint64_t leaf = (index + (u - 1u) * q.trace_stride) & (((uint64_t)1 << L) - 1u);
+                    if (s == 0) { kind = MSG_VALUE; v = tlde[leaf]; }
+                    else { src = TreeNodes{ttree, L, leaf}; nd = L; }
+                } else {
+                    const uint32_t k = u - 1u - tc, depth = L - k;
+                    const uint32_t s4 = depth ? s : s - 1u;      // depth 0: sub 0 is the doubled value
+                    const uint64_t mk = (uint64_t)1 << depth;
+                    const uint64_t idx = index & (mk - 1u);
+                    const uint64_t leaf = (s4 == 2u || s4 == 3u) ? ((idx + mk / 2u) & (mk - 1u)) : idx;
+                    act = k < nl;
+                    if (s4 == 0u || s4 == 2u || s4 == ~0u) { kind = MSG_VALUE; v = act ? lay[q.layer_off[k] + leaf] : 0u; }
+                    else { src = TreeNodes{tre + q.tree_off[k], depth, leaf}; nd = depth; }
+                }
+                if (!act) continue;
+                chan_send(cs, has, kind, src, nd, v);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) chan[j] = __builtin_bswap32(cs[j]);
+    chan[8] = has;
+}
+
+// k_batch_query with a query dimension: block (x + openings * query, member),
+// lane l = tree level l, the index the one k_query_chain drew.  The record of
+// (member, query), rec_words words at out + (member * num_queries + query) *
+// rec_words, is k_batch_query's.
+__global__ __launch_bounds__(64) void k_batch_query_all(QueryPhase q) {
+    const uint32_t L = q.log_n, tc = q.trace_count, opens = tc + q.max_layers;
+    const uint32_t x = blockIdx.x % opens, qi = blockIdx.x / opens, l = threadIdx.x;
+    const uint32_t m = blockIdx.y;
+    const uint32_t nl = q.n_layers[m];
+    if (nl == 0) return;
+    const size_t b = (size_t)q.first + m;
+    const uint64_t index = q.indices[(size_t)m * q.num_queries + qi];
+    uint32_t* rec = q.out + ((size_t)m * q.num_queries + qi) * q.rec_words;
+    uint32_t* tpaths = rec + tc + 2 * q.max_layers;
+    if (x < tc) {
+        const uint64_t leaf = (index + x * q.trace_stride) & (((uint64_t)1 << L) - 1);
+        if (l == 0) rec[x] = q.tlde[b * q.tlde_stride + leaf];
+        if (l >= L) return;
+        const uint32_t* d = q.ttree + b * q.ttree_stride + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
+        uint32_t* o = tpaths + (size_t)x * 8 * L + 8 * l;
+#pragma unroll
+        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+        return;
+    }
+    const uint32_t k = x - tc;
+    if (k >= nl) return;
+    const uint32_t Lk = L - k;
+    const uint64_t mk = (uint64_t)1 << Lk;
+    const uint64_t idx = index % mk, sib = (idx + mk / 2) % mk;
+    const uint32_t* lay = q.layers + b * q.lay_stride + q.layer_off[k];
+    if (l == 0) {
+        rec[tc + 2 * k] = lay[idx];
+        rec[tc + 2 * k + 1] = lay[sib];
+    }
+    if (l >= Lk) return;
+    const uint32_t* tr = q.trees + b * q.tre_stride + q.tree_off[k];
+    uint32_t* paths = tpaths + (size_t)tc * 8 * L + 16 * ((size_t)k * L - (size_t)k * (k - 1) / 2);
+#pragma unroll
+    for (int which = 0; which < 2; which++) {
+        const uint64_t leaf = which ? sib : idx;
+        const uint32_t* d = tr + 8 * (level_offset(Lk, l) + ((leaf >> l) ^ 1u));
+        uint32_t* o = paths + (size_t)which * 8 * Lk + 8 * l;
+#pragma unroll
+        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+    }
+}
+
+void launch_query_phase(const QueryPhase& q, hipStream_t s) {
+    if (!q.members || !q.num_queries) return;
+    hipLaunchKernelGGL(k_query_chain, dim3((q.members + 63u) / 64u), dim3(64), 0, s, q);
+    hipLaunchKernelGGL(k_batch_query_all, dim3((q.trace_count + q.max_layers) * q.num_queries, q.members), dim3(64), 0,
+                       s, q);
 }
 
 }  // namespace fri

@@ -609,10 +609,82 @@ void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_la
         }
     }
 }
+
+// The whole query phase of a batch in ONE fri_batch_query_phase: per member
+// num_queries x (the drawn index, then the round's sends), run by the device
+// on the member's channel.  Every channel then takes over its messages (an
+// index goes to `proof` alone, as receive_random_int(.., true) leaves it) and
+// its final state without hashing.  Returns the members' indices.
+std::vector<std::vector<uint64_t>> query_phase(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_layers,
+                                               size_t num_queries, uint64_t max_index, uint32_t trace_count,
+                                               uint64_t trace_stride, std::vector<FriChannel>& channels) {
+    const size_t B = channels.size(), Q = num_queries, tpath = 32 * size_t{log_n};
+    std::vector<std::vector<uint64_t>> out(B);
+    if (Q == 0) return out;
+    uint64_t generation = 0;
+    uint32_t members = 0, resident_log_n = 0;
+    gpu.check(fri_batch_info(gpu.ctx(), &generation, &members, &resident_log_n), "fri_batch_info");
+    if (members != B) throw Panic("fri_batch_query_phase: one channel per member of the resident batch");
+    if (Q >> 32) throw Panic("fri_batch_query_phase: num_queries out of range");
+    size_t max_layers = 0;
+    for (size_t nl : n_layers) max_layers = std::max(max_layers, nl);
+    size_t fri_bytes = 0;
+    for (size_t k = 0; k < max_layers; k++) fri_bytes += 2 * 32 * (log_n - k);
+    const size_t vstride = trace_count + 2 * max_layers, pstride = std::max<size_t>(trace_count * tpath + fri_bytes, 1);
+    std::vector<fri_channel_state> chan(B);
+    for (size_t b = 0; b < B; b++) {
+        if (channels[b].state.size() != 64) throw Panic("Channel state is not valid hex");     // channel.rs:65
+        auto st = sha::from_hex(channels[b].state);
+        std::memcpy(chan[b].digest, st.data(), 32);
+        chan[b].has_state = 1;
+    }
+    std::vector<uint64_t> indices(B * Q);
+    std::vector<uint32_t> values(B * Q * vstride);
+    std::vector<uint8_t> paths(B * Q * pstride);
+    std::vector<size_t> got(B, 0);
+    gpu.check(fri_batch_query_phase(gpu.ctx(), static_cast<uint32_t>(Q), max_index, chan.data(), nullptr, trace_count,
+                                    trace_stride, indices.data(), values.data(), vstride, paths.data(), pstride,
+                                    got.data()),
+              "fri_batch_query_phase");
+    for (size_t b = 0; b < B; b++) {
+        size_t want = trace_count * tpath;
+        for (size_t k = 0; k < n_layers[b]; k++) want += 2 * 32 * (log_n - k);
+        if (got[b] != want) throw Panic("fri_batch_query_phase: member " + std::to_string(b) + " was not served");
+        FriChannel& ch = channels[b];
+        auto put = [&ch](std::vector<uint8_t> m) {
+            ch.compressed_proof.push_back(m);
+            ch.proof.push_back(std::move(m));
+        };
+        auto bytes = [](const uint8_t* p, size_t len) { return std::vector<uint8_t>(p, p + len); };
+        for (size_t q = 0; q < Q; q++) {
+            const uint32_t* v = values.data() + (b * Q + q) * vstride;
+            const uint8_t* p = paths.data() + (b * Q + q) * pstride;
+            out[b].push_back(indices[b * Q + q]);
+            ch.proof.push_back(FriChannel::be64(indices[b * Q + q]));
+            for (size_t j = 0; j < trace_count; j++) {
+                put(FriChannel::be64(v[j]));
+                put(bytes(p + j * tpath, tpath));
+            }
+            size_t off = trace_count * tpath;
+            for (size_t k = 0; k < n_layers[b]; k++) {
+                const size_t depth = log_n - k, pb = 32 * depth;
+                auto val = FriChannel::be64(v[trace_count + 2 * k]), sval = FriChannel::be64(v[trace_count + 2 * k + 1]);
+                if (depth == 0) put(val);                // fri_commit.rs:147-149: length == 1 sends it first
+                put(val);
+                put(bytes(p + off, pb));
+                put(sval);
+                put(bytes(p + off + pb, pb));
+                off += 2 * pb;
+            }
+        }
+        ch.state = sha::hex(chan[b].digest, 32);
+    }
+    return out;
+}
 }  // namespace
 
 void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
-                        std::vector<FriChannel>& channels) {
+                        std::vector<FriChannel>& channels, bool device_queries) {
     if (channels.size() != proofs.size()) throw Panic("decommit_fri_batch: one channel per proof");
     if (proofs.empty()) return;
     const FRIProof& p0 = proofs[0];
@@ -624,6 +696,10 @@ void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<
         n_layers.push_back(p.n_layers());
     }
     p0.require_resident();
+    if (device_queries) {
+        query_phase(*p0.gpu_, p0.log_n, n_layers, num_queries, max_index, 0, 0, channels);
+        return;
+    }
     std::vector<uint64_t> idx(proofs.size());
     for (size_t q = 0; q < num_queries; q++) {
         for (size_t b = 0; b < proofs.size(); b++) idx[b] = channels[b].receive_random_int(0, max_index, true);
@@ -854,7 +930,7 @@ std::shared_ptr<Gpu> beside_team(uint32_t log_n) {
 
 std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
                                           size_t num_queries, std::vector<FriChannel>& channels, FE offset,
-                                          std::shared_ptr<Gpu> gpu) {
+                                          std::shared_ptr<Gpu> gpu, bool device_queries) {
     if (channels.size() != a1.size()) throw Panic("prove_fibsq_batch: one channel per proof");
     if (a1.empty()) return {};
     const uint32_t L = log_t + log_blowup;
@@ -905,6 +981,11 @@ std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t lo
     for (size_t b = 0; b < B; b++) {
         out[b].fri = FRIProof::mirror_member(res[b], L, gpu, channels[b], gen, b);
         n_layers[b] = res[b].n_layers;
+    }
+    if (device_queries) {
+        auto drawn = query_phase(*gpu, L, n_layers, num_queries, n - 2 * Bl - 1, 3, Bl, channels);
+        for (size_t b = 0; b < B; b++) out[b].queries = std::move(drawn[b]);
+        return out;
     }
     std::vector<uint64_t> idx(B);
     for (size_t q = 0; q < num_queries; q++) {

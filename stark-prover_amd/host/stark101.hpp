@@ -505,10 +505,10 @@ class FRIProof {
     friend std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                   const std::shared_ptr<Gpu>&);
     friend void decommit_fri_layers(size_t, const FRIProof&, FriChannel&);
-    friend void decommit_fri_batch(size_t, size_t, const std::vector<FRIProof>&, std::vector<FriChannel>&);
+    friend void decommit_fri_batch(size_t, size_t, const std::vector<FRIProof>&, std::vector<FriChannel>&, bool);
     friend StarkProof prove_fibsq(FE, uint32_t, uint32_t, size_t, FriChannel&, FE, std::shared_ptr<Gpu>);
     friend std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>&, uint32_t, uint32_t, size_t,
-                                                     std::vector<FriChannel>&, FE, std::shared_ptr<Gpu>);
+                                                     std::vector<FriChannel>&, FE, std::shared_ptr<Gpu>, bool);
     // The proof of a device commit: appends the messages the device sent
     // (root hex per layer, beta per round, final value) to `channel` and
     // takes over its state (fri_commit.rs:84-114).
@@ -558,9 +558,15 @@ void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, F
 // decommit_fri for every member of one batch (`proofs` as fri_commit_batch or
 // prove_fibsq_batch returned them, in member order): per round every channel
 // draws its index, ONE fri_batch_query_round opens them all, and every channel
-// absorbs its openings as decommit_fri_layers sends them.
+// absorbs its openings as decommit_fri_layers sends them.  device_queries:
+// the whole phase, the channels' draws and sends included, in ONE
+// fri_batch_query_phase instead; the channels end byte for byte the same and
+// the host hashes nothing.  Through the Python mirror
+// the whole call loses to the round route at B = 16 and wins from B = 64 at
+// every measured shape (profiles/prove_batch_device_queries.txt, DESIGN.md
+// section 4f); this mirror's route was not measured.
 void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
-                        std::vector<FriChannel>& channels);
+                        std::vector<FriChannel>& channels, bool device_queries = false);
 // The reference's own signature, decommit_fri(num_queries, max_index,
 // &fri_layers, &fri_merkles, &mut channel) (fri_commit.rs:168-174): the
 // commit is found through the device-backed trees (their Gpu and
@@ -609,10 +615,14 @@ StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_qu
 // without one, a one-device Gpu beside a default team).  channels[i] ends
 // byte for byte as prove_fibsq(a1[i], ..., channels[i]) leaves it.  A member
 // whose trace violates the constraints panics after the device calls, naming
-// the member.  An empty a1 returns an empty vector.
+// the member.  An empty a1 returns an empty vector.  device_queries: ONE
+// fri_batch_query_phase replaces the query rounds (three synchronising calls
+// per batch; the host hashes only the trace root and the alphas' draws), with
+// the same channels and StarkProof::queries.
 std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
                                           size_t num_queries, std::vector<FriChannel>& channels,
-                                          FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr);
+                                          FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr,
+                                          bool device_queries = false);
 // CP(x) from f(x), f(gx), f(g^2 x): what layer 0 must hold at a query.
 FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alphas, FE a_last, uint32_t log_t);
 // Verifier of prove_fibsq's transcript: replays the channel, checks the

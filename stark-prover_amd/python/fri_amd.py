@@ -212,6 +212,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_batch_query_round": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8), u32,
                                         ctypes.c_uint64, pu32, sz, ctypes.POINTER(ctypes.c_uint8), sz,
                                         ctypes.POINTER(sz)]),
+        "fri_batch_query_phase": (i32, [vp, u32, ctypes.c_uint64, ctypes.POINTER(ChannelState),
+                                        ctypes.POINTER(ctypes.c_uint8), u32, ctypes.c_uint64,
+                                        ctypes.POINTER(ctypes.c_uint64), pu32, sz, ctypes.POINTER(ctypes.c_uint8), sz,
+                                        ctypes.POINTER(sz)]),
+        "fri_debug_set_query_chunk": (i32, [vp, u32]),
         "fri_debug_transport_log": (i32, [vp, ctypes.POINTER(TransportOp), sz, ctypes.POINTER(sz)]),
         "fri_verify_batch": (i32, [vp, ctypes.POINTER(VerifyShape), u32, ctypes.POINTER(ChannelState), pu32, pu32,
                                    pu32, sz, ctypes.POINTER(ctypes.c_uint64), pu32, sz,
@@ -730,6 +735,72 @@ class Context:
         self._check(rc)
         return values, paths, [int(x) for x in ln][:batch]
 
+    def batch_query_phase(self, num_queries: int, max_index: int, channel_states, skip=None, trace_count: int = 0,
+                          trace_stride: int = 0, max_layers: Optional[int] = None, indices=None, values=None,
+                          paths=None):
+        """fri_batch_query_phase: every query of every member of the resident
+        batch in one call, the members' channels on the device: per member
+        num_queries x (receive_random_int(0, max_index, True), then the
+        round's sends).  ``channel_states``: per member the 32 digest bytes
+        before the first draw, or None for an empty state.  Returns (indices,
+        values, paths, paths_len, states): uint64 (batch, Q), uint32 (batch,
+        Q, values_stride) and uint8 (batch, Q, paths_stride) arrays (the
+        caller's, when given; the layout verify_batch takes), the bytes of one
+        query's paths per member (0: left out, nothing of it written) and the
+        members' states after the last send (a member left out keeps what
+        came in).  ``max_layers`` sizes the arrays made here (default: log_n +
+        1, the most a member can have).  query_phase_messages turns a
+        member's rows into its messages."""
+        _, members, log_n = self.batch_info()
+        batch = len(channel_states)
+        if members and batch != members:
+            raise FriError(FRI_EINVAL, "one channel state per member of the resident batch")
+        q = int(num_queries)
+        if q < 0 or max_index < 0 or max_index >> 64 or q >> 32:
+            raise FriError(FRI_EINVAL, "num_queries and max_index must be non-negative (32 and 64 bits)")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(np.asarray(skip, dtype=np.uint8))
+            if sk.size != batch:
+                raise FriError(FRI_EINVAL, "one skip flag per member")
+        chs = (ChannelState * max(batch, 1))()
+        for b, st in enumerate(channel_states):
+            if st:
+                if len(st) != 32:
+                    raise FriError(FRI_EINVAL, "a channel state is 32 digest bytes or None")
+                ctypes.memmove(chs[b].digest, bytes(st), 32)
+                chs[b].has_state = 1
+        nl = log_n + 1 if max_layers is None else int(max_layers)
+        if indices is None:
+            indices = np.zeros((batch, q), dtype=np.uint64)
+        if values is None:
+            values = np.zeros((batch, q, trace_count + 2 * nl), dtype=np.uint32)
+        if paths is None:
+            paths = np.zeros((batch, q, max(32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(nl)), 1)),
+                             dtype=np.uint8)
+        if indices.dtype != np.uint64 or values.dtype != np.uint32 or paths.dtype != np.uint8 or \
+                indices.shape != (batch, q) or values.ndim != 3 or paths.ndim != 3 or \
+                values.shape[:2] != (batch, q) or paths.shape[:2] != (batch, q) or \
+                not all(a.flags["C_CONTIGUOUS"] for a in (indices, values, paths)):
+            raise FriError(FRI_EINVAL, "indices: C-contiguous uint64 (batch, Q); values: uint32 (batch, Q, stride); "
+                                       "paths: uint8 (batch, Q, stride)")
+        ln = (ctypes.c_size_t * max(batch, 1))()
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        rc = self.lib.fri_batch_query_phase(self.h, q, max_index, chs,
+                                            sk.ctypes.data_as(u8p) if sk is not None else None, trace_count,
+                                            trace_stride, indices.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                            _ptr(values), values.shape[2], paths.ctypes.data_as(u8p), paths.shape[2],
+                                            ln)
+        self.round_needed = int(ln[0]) if rc == FRI_EINVAL else 0     # (too-small strides: the needed paths stride)
+        self._check(rc)
+        states = [bytes(chs[b].digest) if chs[b].has_state else None for b in range(batch)]
+        return indices, values, paths, [int(x) for x in ln][:batch] if q else [0] * batch, states
+
+    def set_query_chunk(self, members: int):
+        """fri_debug_set_query_chunk: members per staging chunk of later
+        batch_query_phase calls (0: chosen by the staging budget)."""
+        self._check(self.lib.fri_debug_set_query_chunk(self.h, members))
+
     def verify_batch(self, shape: "VerifyShape", batch: int, chan, n_layers, a_last, head, head_stride: int,
                      indices, values, values_stride: int, paths, paths_stride: int, verdict=None) -> np.ndarray:
         """fri_verify_batch over the raw ABI: ``shape`` a VerifyShape, ``chan``
@@ -1107,7 +1178,27 @@ class Channel:
         self.proof.append(num.to_bytes(8, "big"))
         return num % P
 
-    def proof_size(self) -> int:                                          # channel.rs:88-90
+    def take_over_queries(self, messages: Sequence[bytes], num_queries: int, state: str) -> None:
+        """The query phase as the device ran it (fri_batch_query_phase), taken
+        over without hashing: ``messages`` are query_phase_messages' --
+        num_queries runs of equal length, each a drawn index (be64) and its
+        openings -- and ``state`` the channel after the last send.  Leaves in
+        ``proof`` and ``compressed_proof`` what receive_random_int(.., True)
+        and send leave there: an index in ``proof`` alone."""
+        if num_queries == 0:
+            if messages:
+                raise FriError(FRI_EINVAL, "messages without a query")
+            return
+        per, rest = divmod(len(messages), num_queries)
+        if rest or per < 1 or len(state) != 64:
+            raise FriError(FRI_EINVAL, "num_queries runs of an index and its openings, and a 64-character state")
+        for i, m in enumerate(messages):
+            self.proof.append(bytes(m))
+            if i % per:
+                self.compressed_proof.append(bytes(m))
+        self.state = state
+
+    def proof_size(self) -> int:                                         # channel.rs:88-90
         return sum(len(b) for b in self.proof)
 
     def compressed_proof_size(self) -> int:                               # channel.rs:93-95
@@ -1729,13 +1820,63 @@ def batch_round_records(values: np.ndarray, paths: np.ndarray, paths_len: int, t
     return trace, _openings(values, raw, n_layers, log_n, trace_count, trace_count * tl)
 
 
+def query_phase_messages(indices, values: np.ndarray, paths: np.ndarray, n_layers: int, log_n: int,
+                         trace_count: int) -> List[bytes]:
+    """One member's rows of Context.batch_query_phase (its Q indices, (Q,
+    stride) values and paths) as the messages of its query phase, in the
+    transcript's order: per query be64(index), trace_count x (value, path),
+    then per layer what _send_openings sends (a one-element layer's value
+    once more first)."""
+    plen = trace_count * 32 * log_n + sum(64 * (log_n - k) for k in range(n_layers))
+    out: List[bytes] = []
+    for q, index in enumerate(indices):
+        out.append(int(index).to_bytes(8, "big"))
+        trace, openings = batch_round_records(values[q], paths[q], plen, trace_count, n_layers, log_n)
+        for v, path in trace:
+            out += [v.to_bytes(8, "big"), path]
+        for val, sval, path, spath in openings:
+            if not path and not spath:
+                out.append(val.to_bytes(8, "big"))
+            out += [val.to_bytes(8, "big"), path, sval.to_bytes(8, "big"), spath]
+    return out
+
+
+def _device_query_phase(ctx: "Context", num_queries: int, max_index: int, fris: Sequence["FRIProof"],
+                        channels: Sequence[Channel], log_n: int, trace_count: int, trace_stride: int):
+    """The query phase of a batch through ONE fri_batch_query_phase: every
+    channel takes over its member's messages and final state.  Returns the
+    members' indices.  A member the device left out raises, as the round
+    route's batch_round_records does."""
+    if num_queries and any(not ch.state for ch in channels):
+        raise FriError(FRI_ESTATE, "Channel state is not valid hex")       # channel.rs:65
+    states = [bytes.fromhex(ch.state) if ch.state else None for ch in channels]
+    idx, values, paths, lens, out = ctx.batch_query_phase(num_queries, max_index, states, trace_count=trace_count,
+                                                          trace_stride=trace_stride,
+                                                          max_layers=max(p.n_layers for p in fris))
+    if num_queries == 0:
+        return [[] for _ in fris]
+    for b, (p, ch) in enumerate(zip(fris, channels)):
+        if lens[b] != trace_count * 32 * log_n + sum(64 * (log_n - k) for k in range(p.n_layers)):
+            raise FriError(FRI_ESTATE, "the record does not hold this many layers (a skipped or failed member?)")
+        ch.take_over_queries(query_phase_messages(idx[b], values[b], paths[b], p.n_layers, log_n, trace_count),
+                             num_queries, out[b].hex())
+    return [[int(i) for i in idx[b]] for b in range(len(fris))]
+
+
 def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIProof"],
-                       channels: Sequence[Channel]) -> None:
+                       channels: Sequence[Channel], device_queries: bool = False) -> None:
     """decommit_fri (fri_commit.rs:168-179) for every member of one batch
     (``proofs`` as fri_commit_batch or prove_fibsq_batch returned them, in
     member order): per round every channel draws its index, ONE
     fri_batch_query_round opens them all, and every channel absorbs its
-    openings as decommit_fri_layers sends them."""
+    openings as decommit_fri_layers sends them.  ``device_queries=True``
+    runs the whole phase, the channels' draws and sends included, in ONE
+    fri_batch_query_phase instead (same transcripts and states; no host
+    hashing).  Measured (profiles/prove_batch_device_queries.txt; log_t 7, 10, 13
+    with 8 and 32 queries, blowup 8): the whole call is slower than the round
+    route at B = 16 (0.47x to 0.71x) and faster from B = 64, the smallest
+    measured size where it wins, at every shape and in both runs (1.1x to
+    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096)."""
     if len(proofs) != len(channels):
         raise FriError(FRI_EINVAL, "one channel per proof")
     if len(proofs) == 0:
@@ -1747,6 +1888,9 @@ def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIPr
     g, members, ln = ctx.batch_info()
     if g != gen or members != len(proofs) or ln != log_n:
         raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
+    if device_queries:
+        _device_query_phase(ctx, num_queries, max_index, proofs, channels, log_n, 0, 0)
+        return
     for _ in range(num_queries):
         idx = [ch.receive_random_int(0, max_index, True) for ch in channels]
         values, paths, lens = ctx.batch_query_round(idx)
@@ -1755,14 +1899,22 @@ def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIPr
 
 
 def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queries: int, channels: Sequence[Channel],
-                      offset: int = GENERATOR, ctx: Optional[Context] = None) -> List[StarkProof]:
+                      offset: int = GENERATOR, ctx: Optional[Context] = None,
+                      device_queries: bool = False) -> List[StarkProof]:
     """prove_fibsq for many proofs of one shape, each with its own a1 and
     channel, in a fixed number of device calls: one fri_trace_commit_batch,
     one fri_fibsq_composition_commit_batch and one fri_batch_query_round per
     query round.  Member i's transcript (``channels[i].proof``) and state are
     what prove_fibsq(a1s[i], ...) into channels[i] gives.  A member whose
     trace violates the constraints raises FriError after the whole batch ran
-    (the message names the member)."""
+    (the message names the member).  ``device_queries=True`` replaces the
+    query rounds by ONE fri_batch_query_phase: three synchronising calls per
+    batch, and the host hashes only the trace root and the alphas' draws.
+    Measured (profiles/prove_batch_device_queries.txt; log_t 7, 10, 13
+    with 8 and 32 queries, blowup 8): the whole call is slower than the round
+    route at B = 16 (0.47x to 0.71x) and faster from B = 64, the smallest
+    measured size where it wins, at every shape and in both runs (1.1x to
+    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096)."""
     if len(a1s) != len(channels):
         raise FriError(FRI_EINVAL, "one channel per proof")
     if len(a1s) == 0:
@@ -1785,6 +1937,9 @@ def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queri
         fri.member = b
         fris.append(fri)
     queries = [[] for _ in a1s]
+    if device_queries:
+        queries = _device_query_phase(ctx, num_queries, n - 2 * B - 1, fris, channels, L, 3, B)
+        num_queries = 0
     for _ in range(num_queries):
         idx = [ch.receive_random_int(0, n - 2 * B - 1, True) for ch in channels]
         values, paths, lens = ctx.batch_query_round(idx, trace_count=3, trace_stride=B)

@@ -19,13 +19,16 @@ log_t in {7, 10, 13} at blowup 8, with 8 and 32 queries, through the Python
 mirror, warm, one process, the median of --reps runs, in microseconds per proof:
   (a) a loop of prove_fibsq (over min(B, 16) members: its cost per proof does
       not depend on B),
-  (b) prove_fibsq_batch of B = 16, 64, 256 members,
+  (b) prove_fibsq_batch of B = 16, 64, 256, 1024, 4096 members (--batches),
+  (c) the same with device_queries=True: the query phase, the channels' draws
+      and sends included, in one fri_batch_query_phase,
 each as the whole mirror call (trace on the host, channel hashing in Python
 included) and as the time inside its device calls alone; (b)'s device time is
-split into the trace commit, the composition commit and the query rounds.
-Every member's transcript of (b) is checked against (a)'s for the members (a) ran.
+split into the trace commit, the composition commit and the query rounds, and
+(c)'s query column is its one query-phase call.  Every member's transcript of
+(b) and of (c) is checked against (a)'s for the members (a) ran.
 
-    python tools/batch_probe.py --prove [--reps 7] [--out profiles/prove_batch.txt]
+    python tools/batch_probe.py --prove [--reps 7] [--batches 16 64 256] [--out profiles/prove_batch.txt]
 
 --verify: the batched verifier against loops of the host verifier, per proof.
 For log_t in {7, 13} at blowup 8, with 8 and 32 queries, B = 16, 64, 256, 4096
@@ -79,7 +82,7 @@ def med_us(fn, reps, per):
 
 
 PROVE_LOG_T = (7, 10, 13)
-PROVE_BATCHES = (16, 64, 256)
+PROVE_BATCHES = (16, 64, 256, 1024, 4096)
 PROVE_QUERIES = (8, 32)
 PROVE_LOG_BLOWUP = 3
 
@@ -88,7 +91,7 @@ class TimedContext:
     """A Context whose device calls of the two provers are timed, by group."""
     GROUPS = {"trace_commit": "trace", "trace_commit_batch": "trace", "fibsq_composition_commit": "comp",
               "fibsq_composition_commit_batch": "comp", "trace_decommit": "query", "decommit_query": "query",
-              "batch_decommit_query": "query", "batch_query_round": "query"}
+              "batch_decommit_query": "query", "batch_query_round": "query", "batch_query_phase": "query"}
 
     def __init__(self, ctx):
         self._ctx = ctx
@@ -118,12 +121,15 @@ def prove_mode(args, reps, say):
     ctx = TimedContext(fri_amd.Context(0, max(PROVE_LOG_T) + lb))
     say(f"batch_probe --prove: {lib.fri_version().decode()}, blowup {1 << lb}, us per proof, median of {reps} "
         "(warm, one process, Python mirror)")
-    say("(a) loop of prove_fibsq  (b) prove_fibsq_batch;  whole: the mirror call;  device: inside its device calls;")
+    say("(a) loop of prove_fibsq  (b) prove_fibsq_batch  (c) prove_fibsq_batch(device_queries=True);")
+    say("whole: the mirror call;  device: inside its device calls;")
     say("trace / comp / query: (b)'s device time in fri_trace_commit_batch, fri_fibsq_composition_commit_batch and")
-    say("the fri_batch_query_round rounds")
+    say("the fri_batch_query_round rounds;  (c) query: its one fri_batch_query_phase call")
     say(f"{'log_t':>5} {'Q':>3} {'B':>4} {'(a) whole':>10} {'(a) device':>10} {'(b) whole':>10} {'(b) device':>10} "
-        f"{'trace':>8} {'comp':>8} {'query':>8} {'device (a)/(b)':>14}")
+        f"{'trace':>8} {'comp':>8} {'query':>8} {'device (a)/(b)':>14} {'(c) whole':>10} {'(c) device':>10} "
+        f"{'(c) query':>10} {'whole (b)/(c)':>13}")
     table = {}
+    batches = tuple(args.batches) if args.batches else PROVE_BATCHES
 
     def measure(fn, per):
         whole, dev, parts = [], [], []
@@ -139,7 +145,7 @@ def prove_mode(args, reps, say):
 
     for log_t in PROVE_LOG_T:
         for Q in PROVE_QUERIES:
-            for B in PROVE_BATCHES:
+            for B in batches:
                 a1s = [1000003 * b + 3141592 for b in range(B)]
                 m = min(B, 16)
                 proofs_a = []
@@ -158,25 +164,41 @@ def prove_mode(args, reps, say):
                     fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx)
                     proofs_b[:] = [ch.proof for ch in chans[:m]]
 
+                proofs_c = []
+
+                def batch_dev():
+                    chans = [fri_amd.Channel() for _ in a1s]
+                    fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx, device_queries=True)
+                    proofs_c[:] = [ch.proof for ch in chans[:m]]
+
                 loop()
                 batch()                               # warm: plans, graphs, the batch's buffers and tables
+                batch_dev()                           # ... and the query phase's staging
                 assert proofs_a == proofs_b, "batch and loop disagree"
+                assert proofs_a == proofs_c, "the device-queries batch and the loop disagree"
                 aw, ad, _ = measure(loop, m)
                 bw, bd, (tr, co, qu) = measure(batch, B)
-                table[(log_t, Q, B)] = (ad, bd, aw, bw)
+                cw, cd, (_, _, cq) = measure(batch_dev, B)
+                table[(log_t, Q, B)] = (ad, bd, aw, bw, cw, cd)
                 say(f"{log_t:>5} {Q:>3} {B:>4} {aw:>10.1f} {ad:>10.1f} {bw:>10.1f} {bd:>10.1f} {tr:>8.1f} {co:>8.1f} "
-                    f"{qu:>8.1f} {ad / bd:>13.1f}x")
+                    f"{qu:>8.1f} {ad / bd:>13.1f}x {cw:>10.1f} {cd:>10.1f} {cq:>10.1f} {bw / cw:>12.2f}x")
     say()
     for log_t in PROVE_LOG_T:
         for Q in PROVE_QUERIES:
-            ad, bd, aw, bw = table[(log_t, Q, 256)]
-            say(f"log_t {log_t}, {Q} queries, B = 256: (b) device {bd:.1f} us is "
-                f"{'faster' if bd < ad else 'SLOWER'} than (a) {ad:.1f} us per proof ({ad / bd:.1f}x); "
-                f"whole {bw:.1f} against {aw:.1f} us ({aw / bw:.1f}x)")
-            wins = [B for B in PROVE_BATCHES if table[(log_t, Q, B)][1] < table[(log_t, Q, B)][0]]
-            wins_w = [B for B in PROVE_BATCHES if table[(log_t, Q, B)][3] < table[(log_t, Q, B)][2]]
+            if (log_t, Q, 256) in table:
+                ad, bd, aw, bw = table[(log_t, Q, 256)][:4]
+                say(f"log_t {log_t}, {Q} queries, B = 256: (b) device {bd:.1f} us is "
+                    f"{'faster' if bd < ad else 'SLOWER'} than (a) {ad:.1f} us per proof ({ad / bd:.1f}x); "
+                    f"whole {bw:.1f} against {aw:.1f} us ({aw / bw:.1f}x)")
+            wins = [B for B in batches if table[(log_t, Q, B)][1] < table[(log_t, Q, B)][0]]
+            wins_w = [B for B in batches if table[(log_t, Q, B)][3] < table[(log_t, Q, B)][2]]
             say(f"    (b) beats (a) from B = {min(wins) if wins else 'none measured'} (device), "
                 f"{min(wins_w) if wins_w else 'none measured'} (whole)")
+            # the smallest B from which (c)'s whole call is faster than (b)'s at every larger measured B
+            lose = [B for B in batches if not table[(log_t, Q, B)][4] < table[(log_t, Q, B)][3]]
+            above = [B for B in batches if not lose or B > max(lose)]
+            say(f"log_t {log_t}, {Q} queries: (c) whole beats (b) whole from B = "
+                f"{min(above) if above else 'none measured'}; slower at B = {lose if lose else 'none measured'}")
     ctx.close()
 
 
@@ -256,6 +278,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--logs", type=int, nargs="*", default=list(LOGS))
     ap.add_argument("--prove", action="store_true", help="the batched prover against a loop of prove_fibsq")
+    ap.add_argument("--batches", type=int, nargs="*", default=None, help="--prove: the batch sizes (default: all)")
     ap.add_argument("--verify", action="store_true", help="the batched verifier against loops of verify_fibsq")
     args = ap.parse_args()
     reps = max(args.reps, 5)
