@@ -653,6 +653,76 @@ int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_t max_index
                           size_t* paths_len);               /* [batch]: bytes per query of member b, 0 = left out */
 int fri_debug_set_query_chunk(fri_ctx* ctx, uint32_t members);     /* 0 = automatic */
 
+/* Proof-of-work grinding before the query phase (the
+ * reference has none: its prover files are empty).  A prover that grinds
+ * `bits` bits sends, after the FRI commit's final value and before the first
+ * query index is drawn, the smallest 8-byte nonce that leaves the channel with
+ * `bits` leading zero bits:
+ *   grind(channel, bits, first = 0):
+ *     v = the smallest integer in [first, last] such that
+ *         D = SHA256(ascii(channel.state) || ascii(hex(be64(v))))
+ *         has its `bits` most significant bits zero
+ *     channel.send(be64(v))                  (channel.rs:35-44: the state becomes D)
+ * with lowercase hex, an empty state for has_state = 0, and 0 <= bits <= 32.
+ * bits = 0 accepts v = first and still sends it.  A verifier checks the zero
+ * bits of the state after the send, not that v is the smallest; the prover
+ * returns the smallest so that transcripts are deterministic.
+ *
+ * fri_grind: chan_in the channel before the send (NULL: Channel::new()).
+ * *found = 1 with *nonce = v and, when chan_out is not NULL, *chan_out the
+ * channel after the send; *found = 0, with *nonce and *chan_out untouched,
+ * when [first, last] holds no such nonce (FRI_OK either way).
+ * fri_grind_batch: fri_grind from first = 0 for every member of chan[batch]:
+ * nonces[b], found[b], and chan[b] replaced by the member's channel after the
+ * send when found[b] (untouched otherwise).
+ *
+ * How it runs.  The state's 64 hex characters are the first block of every
+ * candidate's message, so a candidate costs ONE compression, from the member's
+ * midstate, of a block in which only the nonce's four words vary: one lane per
+ * candidate, on the rate-ordered rounds of the leaf kernels, and only digest
+ * word 0 is formed.  The host walks the range in windows of consecutive
+ * nonces, in rising order; inside a window the hits go through a wave
+ * reduction and a 64-bit atomic minimum per member, and the first window with
+ * a hit ends the member's search, so the answer is the smallest whatever order
+ * the workgroups run in.  (A wave leaves once its next nonces lie above the
+ * current minimum; that only saves work.)  One launch covers every unfinished
+ * member's window and is followed by one read-back of the members' words
+ * through pinned memory.  The automatic window is 8 * 2^bits nonces, from 2^12
+ * up to 2^30 (one launch of 35 ms at the measured rate);
+ * fri_debug_set_grind_window sets log2 of the nonces per launch for the
+ * context's later calls (1..32; 0 = automatic).
+ *
+ * Measured on one MI355X (tools/grind_probe.py, profiles/grind.txt, DESIGN.md
+ * section 4h).  The kernel alone searches 31.0 G nonces/s (2^28 in 8.7 ms, device
+ * events): 1300 VALU instructions = 2038 issue units per nonce, 63.2 T units/s,
+ * 99% of the measured 64 T VALU ceiling (the layer-0 leaf kernel: 94%).  One
+ * whole fri_grind from nonce 0, median over 16 states: 0.049 ms at 16 bits,
+ * 0.109 at 20, 1.25 at 24 and 5.0 at 28 (26.4 G nonces/s of the nonces it had
+ * to look at).  fri_grind_batch at B = 4096: 0.61 us per member at 8 bits, 0.81
+ * at 12, 4.4 at 16 and 51.9 at 20 (20.4 G nonces/s).  Against that the C++
+ * mirror's host loop does 17.7 M nonces/s on one core with the SHA extensions
+ * and 283 M over 16 threads, hashlib 2.7 M.  A call costs about 32 us whatever
+ * the bits up to 12, so the mirrors grind on the host below
+ * GRIND_DEVICE_MIN_BITS, the smallest measured size from which the device call
+ * with its copies wins: 10 bits in the C++ mirror (51.5 us on the host against
+ * 32.4) and 8 in the Python one (78.6 against 32.4).
+ *
+ * FRI_EINVAL, with nothing written: bits > 32, first > last, batch outside
+ * 1..65535, a null nonce / found / chan array.  fri_grind_batch on a multi-GPU
+ * context is FRI_EINVAL and on a profiling context FRI_ESTATE, as
+ * fri_commit_batch; fri_grind runs on rank 0 of a team and, while profiling,
+ * is timed as class "grind" (one span per launch).  The calls read and change
+ * nothing of the resident commit, batch or trace batch: the commit generation
+ * does not move.  The staging (84 bytes per member) belongs to the context and
+ * stays until fri_ctx_destroy. */
+int fri_grind(fri_ctx* ctx, const fri_channel_state* chan_in, uint32_t bits,
+              uint64_t first, uint64_t last,            /* inclusive range, first <= last */
+              uint64_t* nonce, uint32_t* found,
+              fri_channel_state* chan_out);             /* may be NULL; written only when found */
+int fri_grind_batch(fri_ctx* ctx, uint32_t batch, fri_channel_state* chan,   /* [batch] in/out */
+                    uint32_t bits, uint64_t last, uint64_t* nonces, uint32_t* found);
+int fri_debug_set_grind_window(fri_ctx* ctx, uint32_t log_window);   /* nonces per launch; 0 = automatic */
+
 /* Batched verifier: `batch` transcripts of one shape checked in one call, the
  * counterpart of the batched prover.  verify_fri / verify_fibsq of the host
  * mirrors (one transcript, SHA-256 on one CPU core) stay the yardstick: for
@@ -920,7 +990,9 @@ int fri_decommit_query_sharded(fri_ctx* ctx, uint64_t index, uint32_t* values, s
  * Classes: "lde" (LDE NTT), "merkle_layer0_leaf" (layer-0 leaf kernel: leaves
  * + levels 1-4, with its algorithmic bytes), "layer0" (all of layer 0's tree +
  * channel step), "layers" (layers >= 1), and for sharded commits "alltoall"
- * and "gather".  bytes = algorithmic bytes of the span where defined. */
+ * and "gather"; fri_verify_batch adds "verify_chain" and "verify_open",
+ * fri_grind "grind" (one span per window's launches).  bytes = algorithmic
+ * bytes of the span where defined. */
 int fri_set_profiling(fri_ctx* ctx, int enabled);
 int fri_get_profile(fri_ctx* ctx, const char* kernel_class, double* total_ms, uint64_t* launches,
                     uint64_t* bytes);

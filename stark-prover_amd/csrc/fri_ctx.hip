@@ -101,6 +101,7 @@ extern "C" int fri_ctx_destroy(fri_ctx* ctx) {
     plan_free(ctx);
     batch_free(ctx);
     verify_free(ctx);
+    grind_free(ctx);
     for (Lane& ln : ctx->lanes) {
         if (ln.stream) hipStreamDestroy(ln.stream);
         dfree(ctx, ln.d_state);

@@ -13,6 +13,7 @@
 //                      batched prover entry points (trace commit, composition
 //                      commit, query round)
 //   fri_verify.hip     the batched verifier: staging, chunking, the launch pair
+//   fri_grind.hip      proof-of-work grinding: the walk over windows of nonces
 //   fri_lanes.hip      commit lanes, pipelined commits, the input buffer and
 //                      which commit the read-backs serve (residency)
 //   fri_readback.hip   read-backs and decommitment of a committed proof, the
@@ -178,6 +179,17 @@ struct VerifyBufs {
     uint32_t chunk = 0;          // fri_debug_set_verify_chunk: members per launch pair (0: by byte budget)
 };
 
+// Grinding (fri_grind, fri_grind_batch; fri_grind.hip): per member the
+// minimum word, the channel state, the midstate record and the active list in
+// one device buffer, and the pinned mirror of what travels (grown on demand,
+// kept until fri_ctx_destroy).
+struct GrindBufs {
+    uint8_t* dev = nullptr;
+    uint8_t* host = nullptr;     // pinned
+    size_t cap = 0;              // members
+    uint32_t log_window = 0;     // fri_debug_set_grind_window: log2 of the nonces per launch (0: chosen from bits)
+};
+
 struct Team;   // in-process team (defined below)
 
 // Collective transport of the sharded commit: RCCL on the context stream, or
@@ -318,6 +330,7 @@ struct fri_ctx {
     uint32_t commit_log_n = 0;      // codeword log2 of the resident commit
     Batch batch;                    // fri_commit_batch: buffers and residency (fri_batch.hip)
     VerifyBufs verify;              // fri_verify_batch: staging (fri_verify.hip)
+    GrindBufs grind;                // fri_grind, fri_grind_batch: staging (fri_grind.hip)
     uint32_t* interp_tmp = nullptr; // partials of fri_interpolate_points / fri_evaluate, fri_merkle_root's tree (grown on use)
     size_t interp_cap = 0;
     uint32_t roots_leaf = 0;        // fri_debug_set_roots_leaf: roots per leaf subtree (0: FRI_ROOTS_LEAF)
@@ -684,6 +697,9 @@ void batch_free(fri_ctx* ctx);                // fri_ctx_destroy
 
 // ---- fri_verify.hip
 void verify_free(fri_ctx* ctx);               // fri_ctx_destroy
+
+// ---- fri_grind.hip
+void grind_free(fri_ctx* ctx);                // fri_ctx_destroy
 
 int input_checksum(fri_ctx* ctx, const uint32_t* d_src, size_t d, uint64_t* out);   // (synchronous)
 

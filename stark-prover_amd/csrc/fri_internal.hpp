@@ -385,6 +385,36 @@ struct QueryPhase {
 };
 void launch_query_phase(const QueryPhase& q, hipStream_t s);
 
+// Proof-of-work grinding (fri_grind, fri_grind_batch): the
+// smallest nonce whose send leaves the channel state with leading zero bits.
+// A member's record is what every candidate shares: the SHA-256 state before
+// the nonce's block (the midstate after the state's 64 hex characters, or the
+// IV for an empty state) and the message length in bits (640 or 128).
+struct GrindMember {
+    uint32_t mid[8];
+    uint32_t len_bits;
+};
+// One window of consecutive nonces hi * 2^32 + lo0 + i, i <= last_idx, that
+// does not cross a multiple of 2^32, searched for every member j < n_active
+// (member active[j], or j itself when active is null).  best[m] takes the
+// smallest i whose digest word 0 has no bit of `mask` set (64-bit atomic min;
+// ~0 = none so far); the members that found one get their channel state after
+// the send in chan[m] (9 words, fri_channel_state).
+struct GrindTask {
+    const GrindMember* mem;
+    unsigned long long* best;
+    const uint32_t* active;
+    uint32_t* chan;
+    uint32_t hi, lo0, last_idx;
+    uint32_t rows;               // ceil(((lo0 & 63) + last_idx + 1) / 64): the window in rows of one nonce per lane
+    uint32_t mask;
+    uint32_t n_active;
+};
+// chan: `members` channel states; fills mem and sets best to ~0
+void launch_grind_prep(const uint32_t* chan, GrindMember* mem, unsigned long long* best, uint32_t members,
+                       hipStream_t s);
+void launch_grind(const GrindTask& q, hipStream_t s);
+
 // fri_verify_kernels.hip — the batched verifier (fri_verify_batch): `members`
 // transcripts of one shape, packed as fri_amd.h describes, in device memory
 // with compact strides.  Both kernels OR what they find into verdict[b]

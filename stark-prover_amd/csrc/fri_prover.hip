@@ -1,6 +1,7 @@
 // fri_prover.hip — prover slice around the FRI commit (SURVEY.md §8(f) rank 2,
 // BASELINE configs[3]): the STARK-101 FibonacciSq composition polynomial in
-// evaluation form on the LDE coset, and the trace-tree decommitment gather.
+// evaluation form on the LDE coset, the trace-tree decommitment gather, the
+// batch's query phase and the proof-of-work grinding before it.
 //
 // The reference's src/prover, src/trace and src/composition are empty files;
 // the constraint system is STARK-101's (the crate is `stark-101`,
@@ -17,6 +18,7 @@
 // over CP_K consecutive points per lane, one Fermat inverse per lane).
 #include "fri_internal.hpp"
 #include "chan_send.hpp"
+#include "sha256_fast.hpp"
 
 namespace fri {
 
@@ -297,6 +299,172 @@ void launch_query_phase(const QueryPhase& q, hipStream_t s) {
     hipLaunchKernelGGL(k_query_chain, dim3((q.members + 63u) / 64u), dim3(64), 0, s, q);
     hipLaunchKernelGGL(k_batch_query_all, dim3((q.trace_count + q.max_layers) * q.num_queries, q.members), dim3(64), 0,
                        s, q);
+}
+
+// ------------------------------------------------- grinding ---
+// fri_grind / fri_grind_batch: the smallest nonce v such that
+//     SHA256(ascii(state) || ascii(hex(be64(v))))
+// has its `bits` most significant bits zero (the state after channel.send of
+// the 8-byte nonce, channel.rs:35-44).  The state's 64 hex characters are the
+// first block of every candidate, so a candidate costs one compression, from
+// the member's midstate, of a block of which only W0..W3 (the nonce's 16 hex
+// characters) vary: W4 is the padding bit, W15 the length, the rest zero.
+
+// 16 bits -> 4 lowercase hex characters, one big-endian message word (SWAR:
+// the nibbles spread to bytes, '0' + n, and 0x27 more from 10 up)
+__device__ __forceinline__ uint32_t hex4(uint32_t x) {
+    const uint32_t t = ((x & 0xF000u) << 12) | ((x & 0x0F00u) << 8) | ((x & 0x00F0u) << 4) | (x & 0x000Fu);
+    return t + 0x30303030u + (((t + 0x06060606u) >> 4) & 0x01010101u) * 0x27u;
+}
+
+// One lane per member: the midstate of its channel state and its length word.
+__global__ __launch_bounds__(256) void k_grind_prep(const uint32_t* __restrict__ chan, GrindMember* __restrict__ mem,
+                                                    unsigned long long* __restrict__ best, uint32_t members) {
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m >= members) return;
+    const uint32_t* c = chan + (size_t)m * 9u;
+    uint32_t st[8];
+    sha::init(st);
+    uint32_t len = 128u;
+    if (c[8]) {
+        uint32_t w[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) hex2(__builtin_bswap32(c[j]), w[2 * j], w[2 * j + 1]);
+        sha::compress(st, w);
+        len = 640u;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) mem[m].mid[j] = st[j];
+    mem[m].len_bits = len;
+    best[m] = ~0ull;
+}
+
+// Digest word 0 of the nonce's block from the midstate.  The rate-ordered
+// rounds of the leaf kernels (sha256_fast.hpp); the schedule stays in C so
+// that its zero words fold and what depends on m0, m1 and the length alone
+// leaves the caller's loop.  Rounds 0-1 see only m0 and m1 (the same for a
+// whole window) and stay in C for the same reason; round 63 does so that the
+// unused e of the last round goes.  k15 = K[15] + len_bits, in an SGPR.
+__device__ __forceinline__ uint32_t grind_word0(const uint32_t mid[8], uint32_t m0, uint32_t m1, uint32_t m2,
+                                                uint32_t m3, uint32_t len_bits, uint32_t k15) {
+    using namespace shaf;
+    uint32_t w[16] = {m0, m1, m2, m3, 0x80000000u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, len_bits};
+    uint32_t a = mid[0], b = mid[1], c = mid[2], d = mid[3], e = mid[4], f = mid[5], g = mid[6], h = mid[7];
+#pragma unroll
+    for (int t = 0; t < 64; t += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int tt = t + u;
+            if (tt < 2) {
+                SHAF_ROUND8(SHAF_RND_C, u, sha::K(tt) + w[tt])
+            } else if (tt < 4) {
+                SHAF_ROUND8(SHAF_RND_W, u, w[tt], sha::K(tt))
+            } else if (tt < 15) {
+                SHAF_ROUND8(SHAF_RND_K, u, sha::K(tt) + w[tt])
+            } else if (tt == 15) {
+                SHAF_ROUND8(SHAF_RND_K, u, k15)
+            } else {
+                const uint32_t wt = w[tt & 15] + s0(w[(tt - 15) & 15]) + w[(tt - 7) & 15] + s1(w[(tt - 2) & 15]);
+                w[tt & 15] = wt;
+                if (tt < 63) {
+                    SHAF_ROUND8(SHAF_RND_W, u, wt, sha::K(tt))
+                } else {
+                    SHAF_ROUND8(SHAF_RND_C, u, sha::K(tt) + wt)
+                }
+            }
+        }
+    }
+    return mid[0] + a;
+}
+
+// Block (x, j): member j of the active list, waves blockIdx.x * 4 .. + 3 of
+// gridDim.x * 4.  The window is cut into rows of 64 consecutive nonces, one
+// per lane, aligned to 64 (the lanes below lo0 in the first row and past the
+// end in the last sit out), so a nonce's low six bits are its lane: the last
+// hex character is the lane's own and W2 and half of W3 are the row's.  Wave
+// v takes rows v, v + waves, ..: ascending, so after its first hit nothing it
+// could still find is smaller, and a row that starts above the member's
+// current minimum (a relaxed load, issued a row ahead) cannot lower it.  Both
+// exits only save work: a row is skipped only when all of it lies above a
+// value the minimum has already reached.  The lowest hit lane of a row holds
+// the row's smallest hit and alone goes to the atomic.
+__global__ __launch_bounds__(256) void k_grind(GrindTask q) {
+    const uint32_t j = blockIdx.y;
+    const uint32_t m = q.active ? q.active[j] : j;
+    const GrindMember* gm = q.mem + m;
+    uint32_t mid[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) mid[i] = __builtin_amdgcn_readfirstlane(gm->mid[i]);
+    const uint32_t len_bits = __builtin_amdgcn_readfirstlane(gm->len_bits);
+    const uint32_t k15 = __builtin_amdgcn_readfirstlane(sha::K(15) + len_bits);
+    unsigned long long* best = q.best + m;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t waves = gridDim.x * 4u;
+    uint32_t m0, m1;
+    hex2(q.hi, m0, m1);
+    const uint32_t base = q.lo0 & ~63u, skew = q.lo0 & 63u;
+    const uint32_t c0 = hexch(lane & 15u);
+    unsigned long long cur = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll 1
+    for (uint32_t row = wave; row < q.rows; row += waves) {
+        const uint32_t rel0 = row * 64u;                       // lane 0's nonce, counted from base
+        if ((unsigned long long)(rel0 > skew ? rel0 - skew : 0u) > cur) break;
+        const unsigned long long nxt = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t lo_u = base + rel0;                     // low six bits zero: the lanes'
+        const uint32_t m2 = hex4(lo_u >> 16);
+        const uint32_t n1 = ((lo_u >> 4) & 0xCu) | (lane >> 4);
+        const uint32_t m3 = (hex4(lo_u & 0xFFFFu) & 0xFFFF0000u) | (hexch(n1) << 8) | c0;
+        const uint32_t h0 = grind_word0(mid, m0, m1, m2, m3, len_bits, k15);
+        const uint32_t idx = rel0 + lane;
+        const bool hit = idx >= skew && idx - skew <= q.last_idx && (h0 & q.mask) == 0u;
+        const unsigned long long hits = __ballot(hit);
+        if (hits) {
+            if (lane == (uint32_t)__builtin_ctzll(hits))
+                __hip_atomic_fetch_min(best, (unsigned long long)(idx - skew), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        cur = nxt;
+    }
+}
+
+// One lane per active member: the whole digest of the nonce it found, if any,
+// as its channel state after the send.
+__global__ __launch_bounds__(64) void k_grind_finish(GrindTask q) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= q.n_active) return;
+    const uint32_t m = q.active ? q.active[j] : j;
+    const unsigned long long b = q.best[m];
+    if (b == ~0ull) return;
+    const GrindMember gm = q.mem[m];
+    uint32_t w[16] = {0u, 0u, 0u, 0u, 0x80000000u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, gm.len_bits};
+    hex2(q.hi, w[0], w[1]);
+    hex2(q.lo0 + (uint32_t)b, w[2], w[3]);
+    uint32_t st[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = gm.mid[i];
+    sha::compress(st, w);
+    uint32_t* c = q.chan + (size_t)m * 9u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) c[i] = __builtin_bswap32(st[i]);
+    c[8] = 1u;
+}
+
+void launch_grind_prep(const uint32_t* chan, GrindMember* mem, unsigned long long* best, uint32_t members,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(k_grind_prep, dim3((members + 255u) / 256u), dim3(256), 0, s, chan, mem, best, members);
+}
+
+// The search of one window, then the states of the members that found a nonce.
+// 2048 workgroups of four waves fill the chip at eight waves per SIMD; a batch
+// shares them among its members, at least one workgroup each.
+void launch_grind(const GrindTask& q, hipStream_t s) {
+    if (!q.n_active || !q.rows) return;
+    const uint32_t share = 2048u / q.n_active ? 2048u / q.n_active : 1u, want = (q.rows + 3u) / 4u;
+    const uint32_t gx = want < share ? want : share;
+    hipLaunchKernelGGL(k_grind, dim3(gx, q.n_active), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(k_grind_finish, dim3((q.n_active + 63u) / 64u), dim3(64), 0, s, q);
 }
 
 }  // namespace fri

@@ -227,6 +227,104 @@ std::shared_ptr<Gpu> Gpu::thread_default(uint32_t log_n) {
     return g;
 }
 
+// ------------------------------------------------------------------ grinding
+namespace {
+uint32_t g_grind_device_min_bits = GRIND_DEVICE_MIN_BITS;
+
+fri_channel_state abi_state(const std::string& state) {
+    fri_channel_state c{};
+    if (state.empty()) return c;
+    if (state.size() != 64) throw Panic("Channel state is not valid hex");
+    auto st = sha::from_hex(state);
+    std::memcpy(c.digest, st.data(), 32);
+    c.has_state = 1;
+    return c;
+}
+void check_grinding_bits(uint32_t bits) {
+    if (bits > GRIND_MAX_BITS) throw Panic("grinding_bits must be 0..32");
+}
+}  // namespace
+
+uint32_t grind_device_min_bits() { return g_grind_device_min_bits; }
+void set_grind_device_min_bits(uint32_t bits) { g_grind_device_min_bits = bits; }
+
+bool state_has_zero_bits(const std::string& state, uint32_t bits) {
+    if (state.size() != 64 || bits > 256) return false;
+    const auto d = sha::from_hex(state);
+    for (uint32_t i = 0; i < bits; i++)
+        if (d[i / 8] >> (7 - i % 8) & 1) return false;
+    return true;
+}
+
+bool grind_host(const std::string& state, uint32_t bits, uint64_t first, uint64_t last, uint64_t* nonce) {
+    if (bits > GRIND_MAX_BITS || first > last) throw Panic("grind: bits must be 0..32 and first <= last");
+    // the state's whole blocks once; then per nonce the tail: the rest of the
+    // state, the nonce's 16 hex characters, the padding and the length
+    uint32_t mid[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    const size_t full = state.size() / 64, rem = state.size() - 64 * full, len = state.size() + 16;
+    compress_blocks(mid, reinterpret_cast<const uint8_t*>(state.data()), full);
+    uint8_t tail[128] = {0};
+    std::memcpy(tail, state.data() + 64 * full, rem);
+    tail[rem + 16] = 0x80;
+    const size_t tl = rem + 16 + 9 <= 64 ? 64 : 128;                    // rem < 64
+    for (int i = 0; i < 8; i++) tail[tl - 1 - i] = static_cast<uint8_t>(static_cast<uint64_t>(len) * 8 >> (8 * i));
+    const uint32_t mask = bits ? ~uint32_t{0} << (32 - bits) : 0;
+    static const char* digits = "0123456789abcdef";
+    for (uint64_t v = first;; v++) {
+        for (int i = 0; i < 16; i++) tail[rem + i] = static_cast<uint8_t>(digits[v >> (60 - 4 * i) & 15]);
+        uint32_t h[8];
+        std::memcpy(h, mid, sizeof h);
+        compress_blocks(h, tail, tl / 64);
+        if ((h[0] & mask) == 0) {
+            *nonce = v;
+            return true;
+        }
+        if (v == last) return false;
+    }
+}
+
+bool grind_device(const Gpu& gpu, const std::string& state, uint32_t bits, uint64_t first, uint64_t last,
+                  uint64_t* nonce) {
+    const fri_channel_state cin = abi_state(state);
+    uint32_t found = 0;
+    gpu.check(fri_grind(gpu.ctx(), &cin, bits, first, last, nonce, &found, nullptr), "fri_grind");
+    return found != 0;
+}
+
+namespace {
+// A prover's grinding step: nothing for 0 bits, else Channel::grind, on the
+// host below grind_device_min_bits() and on the device from it up.
+void grind_step(FriChannel& channel, uint32_t bits, const std::shared_ptr<Gpu>& gpu) {
+    check_grinding_bits(bits);
+    if (bits) channel.grind(bits, bits >= g_grind_device_min_bits ? gpu : nullptr);
+}
+// ... for every member's channel: on the device ONE fri_grind_batch on the
+// members' states; every channel then sends its nonce and must arrive at the
+// state the device returned.
+void grind_step_batch(std::vector<FriChannel>& channels, uint32_t bits, const Gpu& gpu) {
+    check_grinding_bits(bits);
+    if (!bits) return;
+    if (bits < g_grind_device_min_bits) {
+        for (auto& ch : channels) ch.grind(bits);
+        return;
+    }
+    const size_t B = channels.size();
+    std::vector<fri_channel_state> chan(B);
+    for (size_t b = 0; b < B; b++) chan[b] = abi_state(channels[b].state);
+    std::vector<uint64_t> nonces(B);
+    std::vector<uint32_t> found(B);
+    gpu.check(fri_grind_batch(gpu.ctx(), static_cast<uint32_t>(B), chan.data(), bits, ~uint64_t{0}, nonces.data(),
+                              found.data()),
+              "fri_grind_batch");
+    for (size_t b = 0; b < B; b++) {
+        if (!found[b]) throw Panic("grind: member " + std::to_string(b) + ": no nonce gives the state the zero bits");
+        channels[b].send(FriChannel::be64(nonces[b]));
+        if (channels[b].state != sha::hex(chan[b].digest, 32) || !state_has_zero_bits(channels[b].state, bits))
+            throw Panic("grind: member " + std::to_string(b) + ": the state after the nonce is not the device's");
+    }
+}
+}  // namespace
+
 namespace {
 uint32_t ceil_log2(size_t n) {
     uint32_t l = 0;
@@ -555,7 +653,9 @@ void decommit_fri_layers(size_t index, const FRIProof& proof, FriChannel& channe
     decommit_query(*proof.gpu_, proof.log_n, proof.n_layers(), index, channel, nullptr, proof.member_);
 }
 
-void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel) {
+void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel,
+                  uint32_t grinding_bits) {
+    grind_step(channel, grinding_bits, proof.gpu_);
     for (size_t q = 0; q < num_queries; q++) {
         const uint64_t idx = channel.receive_random_int(0, max_index, true);
         decommit_fri_layers(idx, proof, channel);
@@ -684,7 +784,8 @@ std::vector<std::vector<uint64_t>> query_phase(const Gpu& gpu, uint32_t log_n, c
 }  // namespace
 
 void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
-                        std::vector<FriChannel>& channels, bool device_queries) {
+                        std::vector<FriChannel>& channels, bool device_queries, uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     if (channels.size() != proofs.size()) throw Panic("decommit_fri_batch: one channel per proof");
     if (proofs.empty()) return;
     const FRIProof& p0 = proofs[0];
@@ -696,6 +797,7 @@ void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<
         n_layers.push_back(p.n_layers());
     }
     p0.require_resident();
+    grind_step_batch(channels, grinding_bits, *p0.gpu_);
     if (device_queries) {
         query_phase(*p0.gpu_, p0.log_n, n_layers, num_queries, max_index, 0, 0, channels);
         return;
@@ -708,7 +810,7 @@ void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<
 }
 
 void decommit_fri(size_t num_queries, size_t max_index, const std::vector<std::vector<FE>>& fri_layers,
-                  const std::vector<MerkleTree>& fri_merkles, FriChannel& channel) {
+                  const std::vector<MerkleTree>& fri_merkles, FriChannel& channel, uint32_t grinding_bits) {
     if (fri_merkles.empty()) throw Panic("decommit_fri: no FRI layers");
     if (fri_layers.size() != fri_merkles.size()) throw Panic("decommit_fri: one Merkle tree per FRI layer");
     const MerkleTree& t0 = fri_merkles[0];
@@ -731,6 +833,7 @@ void decommit_fri(size_t num_queries, size_t max_index, const std::vector<std::v
     }
     if (n_layers != fri_merkles.size() || fri_layers[0].size() != (size_t{1} << log_n))
         throw Panic("decommit_fri: the resident commit is not the one these trees belong to");
+    grind_step(channel, grinding_bits, t0.gpu_);
     for (size_t q = 0; q < num_queries; q++) {
         const uint64_t idx = channel.receive_random_int(0, max_index, true);
         decommit_query(gpu, log_n, n_layers, idx, channel, &fri_layers, t0.member_);
@@ -776,7 +879,9 @@ using Take = std::function<const std::vector<uint8_t>&()>;
 bool verify_transcript(const Msgs& msgs, uint32_t log_n, size_t n_layers, size_t num_queries, size_t max_index,
                        FE offset, const std::string& channel_state,
                        const std::function<void(const Take&, FriChannel&)>& pre_commit,
-                       const std::function<int64_t(const Take&, FriChannel&, uint64_t)>& on_query) {
+                       const std::function<int64_t(const Take&, FriChannel&, uint64_t)>& on_query,
+                       uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     if (n_layers == 0 || n_layers > log_n + 1u) return false;
     size_t pos = 0;
     Take take = [&]() -> const std::vector<uint8_t>& {
@@ -807,6 +912,12 @@ bool verify_transcript(const Msgs& msgs, uint32_t log_n, size_t n_layers, size_t
         if (fin.size() != 8) return false;
         const uint64_t final_value = be_u64(fin);
         ch.send(fin);
+        if (grinding_bits) {
+            const auto& nonce = take();
+            if (nonce.size() != 8) return false;
+            ch.send(nonce);
+            if (!state_has_zero_bits(ch.state, grinding_bits)) return false;
+        }
         const FE inv2 = FE(2).inverse();
         for (size_t q = 0; q < num_queries; q++) {
             const uint64_t idx = ch.receive_random_int(0, max_index, true);
@@ -857,8 +968,9 @@ bool verify_transcript(const Msgs& msgs, uint32_t log_n, size_t n_layers, size_t
 }  // namespace
 
 bool verify_fri(const Msgs& msgs, uint32_t log_n, size_t n_layers, size_t num_queries, size_t max_index, FE offset,
-                const std::string& channel_state) {
-    return verify_transcript(msgs, log_n, n_layers, num_queries, max_index, offset, channel_state, nullptr, nullptr);
+                const std::string& channel_state, uint32_t grinding_bits) {
+    return verify_transcript(msgs, log_n, n_layers, num_queries, max_index, offset, channel_state, nullptr, nullptr,
+                             grinding_bits);
 }
 
 // ----------------------------------------------------------- prover slice
@@ -869,7 +981,8 @@ std::vector<FE> fibsq_trace(FE a1, uint32_t log_t) {
 }
 
 StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_queries, FriChannel& channel, FE offset,
-                       std::shared_ptr<Gpu> gpu) {
+                       std::shared_ptr<Gpu> gpu, uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     const uint32_t L = log_t + log_blowup;
     const uint64_t B = uint64_t{1} << log_blowup, n = uint64_t{1} << L;
     if (!gpu) gpu = Gpu::thread_default(L);
@@ -898,6 +1011,7 @@ StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_qu
     gpu->check(fri_fibsq_composition_commit(gpu->ctx(), log_t, log_blowup, off, trace.back(), al, &cin, 0, &res),
                "fri_fibsq_composition_commit");
     sp.fri = FRIProof::mirror(res, L, gpu, channel);
+    grind_step(channel, grinding_bits, gpu);
     std::vector<uint32_t> vals(3);
     std::vector<uint8_t> paths(3 * 32 * size_t{L});
     for (size_t q = 0; q < num_queries; q++) {
@@ -930,7 +1044,8 @@ std::shared_ptr<Gpu> beside_team(uint32_t log_n) {
 
 std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
                                           size_t num_queries, std::vector<FriChannel>& channels, FE offset,
-                                          std::shared_ptr<Gpu> gpu, bool device_queries) {
+                                          std::shared_ptr<Gpu> gpu, bool device_queries, uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     if (channels.size() != a1.size()) throw Panic("prove_fibsq_batch: one channel per proof");
     if (a1.empty()) return {};
     const uint32_t L = log_t + log_blowup;
@@ -982,6 +1097,7 @@ std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t lo
         out[b].fri = FRIProof::mirror_member(res[b], L, gpu, channels[b], gen, b);
         n_layers[b] = res[b].n_layers;
     }
+    grind_step_batch(channels, grinding_bits, *gpu);
     if (device_queries) {
         auto drawn = query_phase(*gpu, L, n_layers, num_queries, n - 2 * Bl - 1, 3, Bl, channels);
         for (size_t b = 0; b < B; b++) out[b].queries = std::move(drawn[b]);
@@ -1008,7 +1124,7 @@ FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alph
 }
 
 bool verify_fibsq(const Msgs& msgs, FE a_last, uint32_t log_t, uint32_t log_blowup, size_t num_queries,
-                  size_t n_layers, FE offset, const std::string& channel_state) {
+                  size_t n_layers, FE offset, const std::string& channel_state, uint32_t grinding_bits) {
     const uint32_t L = log_t + log_blowup;
     const uint64_t B = uint64_t{1} << log_blowup, n = uint64_t{1} << L;
     std::array<uint8_t, 32> root{};
@@ -1039,7 +1155,8 @@ bool verify_fibsq(const Msgs& msgs, FE a_last, uint32_t log_t, uint32_t log_blow
         const FE x = offset * omega(L).pow(idx);
         return static_cast<int64_t>(fibsq_composition_at(f[0], f[1], f[2], x, alphas, a_last, log_t).value());
     };
-    return verify_transcript(msgs, L, n_layers, num_queries, n - 2 * B - 1, offset, channel_state, pre, on_query);
+    return verify_transcript(msgs, L, n_layers, num_queries, n - 2 * B - 1, offset, channel_state, pre, on_query,
+                             grinding_bits);
 }
 
 // ------------------------------------------------------- batched verifier

@@ -318,6 +318,33 @@ struct CosetFri {
     }
 };
 
+// ------------------------------------------------------------------ grinding
+// Proof of work before the query phase (include/fri_amd.h, fri_grind; DESIGN.md
+// section 4h; the reference has none): the smallest nonce in [first, last]
+// such that sha256(state || hex(be64(nonce))), the state after
+// channel.send(be64(nonce)), has its `bits` (0..32) most significant bits
+// zero.  false: the range holds none.  grind_host is a loop on this mirror's
+// SHA-256 (one compression per nonce from the state's midstate); grind_device
+// is fri_grind on `gpu`.  The provers below grind on the host under
+// grind_device_min_bits() bits and on the device from it up;
+// GRIND_DEVICE_MIN_BITS, its default, is the smallest measured size from which
+// the whole device call (about 32 us with its launches, read-back and copies)
+// beats grind_host on one core with the SHA extensions (51.5 us at 10 bits,
+// 17.5 at 8; profiles/grind.txt, table (v), rows 8 and 10, from
+// tools/grind_probe.py; the device column there is the Python mirror's call,
+// ctypes included, so the threshold is on the safe side for this mirror);
+// set_grind_device_min_bits is a test and measurement hook.
+class Gpu;
+constexpr uint32_t GRIND_MAX_BITS = 32;
+constexpr uint32_t GRIND_DEVICE_MIN_BITS = 10;
+uint32_t grind_device_min_bits();
+void set_grind_device_min_bits(uint32_t bits);
+bool grind_host(const std::string& state, uint32_t bits, uint64_t first, uint64_t last, uint64_t* nonce);
+bool grind_device(const Gpu& gpu, const std::string& state, uint32_t bits, uint64_t first, uint64_t last,
+                  uint64_t* nonce);
+// the `bits` most significant bits of a state (64 hex characters) are zero
+bool state_has_zero_bits(const std::string& state, uint32_t bits);
+
 // ------------------------------------------------------------------- Channel
 // channel.rs:14-96.  state is "" or the 64-char lowercase hex of a digest.
 template <uint64_t MODULUS>
@@ -355,6 +382,19 @@ class Channel {
         uint64_t num = receive_random_int(0, MODULUS - 1, false);
         proof.push_back(be64(num));
         return FieldElement<MODULUS>(num);
+    }
+    // Grinding: finds the smallest nonce >= first whose send leaves the state
+    // with `bits` leading zero bits (on the host, or on `gpu` when given),
+    // sends it as an 8-byte message, checks the new state and returns it.
+    uint64_t grind(uint32_t bits, const std::shared_ptr<Gpu>& gpu = nullptr, uint64_t first = 0) {
+        if (bits > GRIND_MAX_BITS) throw Panic("grind: bits must be 0..32");
+        uint64_t nonce = 0;
+        const bool found = gpu ? grind_device(*gpu, state, bits, first, ~uint64_t{0}, &nonce)
+                               : grind_host(state, bits, first, ~uint64_t{0}, &nonce);
+        if (!found) throw Panic("grind: no nonce in range gives the state the zero bits");
+        send(be64(nonce));
+        if (!state_has_zero_bits(state, bits)) throw Panic("grind: the state after the nonce lacks the zero bits");
+        return nonce;
     }
     size_t proof_size() const { return total(proof); }                       // channel.rs:88-90
     size_t compressed_proof_size() const { return total(compressed_proof); } // channel.rs:93-95
@@ -467,7 +507,7 @@ class MerkleTree {
   private:
     friend class FRIProof;
     friend void decommit_fri(size_t, size_t, const std::vector<std::vector<FE>>&, const std::vector<MerkleTree>&,
-                             FriChannel&);
+                             FriChannel&, uint32_t);
     friend FRIProof fri_commit_coset(const Poly&, uint32_t, FE, FriChannel&, const std::shared_ptr<Gpu>&);
     friend std::vector<FRIProof> fri_commit_pipelined(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                       const std::shared_ptr<Gpu>&);
@@ -505,10 +545,13 @@ class FRIProof {
     friend std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>&, uint32_t, FE, std::vector<FriChannel>&,
                                                   const std::shared_ptr<Gpu>&);
     friend void decommit_fri_layers(size_t, const FRIProof&, FriChannel&);
-    friend void decommit_fri_batch(size_t, size_t, const std::vector<FRIProof>&, std::vector<FriChannel>&, bool);
-    friend StarkProof prove_fibsq(FE, uint32_t, uint32_t, size_t, FriChannel&, FE, std::shared_ptr<Gpu>);
+    friend void decommit_fri(size_t, size_t, const FRIProof&, FriChannel&, uint32_t);
+    friend void decommit_fri_batch(size_t, size_t, const std::vector<FRIProof>&, std::vector<FriChannel>&, bool,
+                                   uint32_t);
+    friend StarkProof prove_fibsq(FE, uint32_t, uint32_t, size_t, FriChannel&, FE, std::shared_ptr<Gpu>, uint32_t);
     friend std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>&, uint32_t, uint32_t, size_t,
-                                                     std::vector<FriChannel>&, FE, std::shared_ptr<Gpu>, bool);
+                                                     std::vector<FriChannel>&, FE, std::shared_ptr<Gpu>, bool,
+                                                     uint32_t);
     // The proof of a device commit: appends the messages the device sent
     // (root hex per layer, beta per round, final value) to `channel` and
     // takes over its state (fri_commit.rs:84-114).
@@ -554,7 +597,10 @@ std::vector<FRIProof> fri_commit_batch(const std::vector<Poly>& polys, uint32_t 
 
 // fri_commit.rs:137-179 over the device-resident layers and trees.
 void decommit_fri_layers(size_t index, const FRIProof& proof, FriChannel& channel);
-void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel);
+// grinding_bits > 0 (here and below): the channel first grinds that many bits
+// (Channel::grind), after the commit's final value and before the first index.
+void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, FriChannel& channel,
+                  uint32_t grinding_bits = 0);
 // decommit_fri for every member of one batch (`proofs` as fri_commit_batch or
 // prove_fibsq_batch returned them, in member order): per round every channel
 // draws its index, ONE fri_batch_query_round opens them all, and every channel
@@ -565,8 +611,10 @@ void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, F
 // the whole call loses to the round route at B = 16 and wins from B = 64 at
 // every measured shape (profiles/prove_batch_device_queries.txt, DESIGN.md
 // section 4f); this mirror's route was not measured.
+// grinding_bits > 0: every channel first grinds, from grind_device_min_bits()
+// up in ONE fri_grind_batch, by either route.
 void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<FRIProof>& proofs,
-                        std::vector<FriChannel>& channels, bool device_queries = false);
+                        std::vector<FriChannel>& channels, bool device_queries = false, uint32_t grinding_bits = 0);
 // The reference's own signature, decommit_fri(num_queries, max_index,
 // &fri_layers, &fri_merkles, &mut channel) (fri_commit.rs:168-174): the
 // commit is found through the device-backed trees (their Gpu and
@@ -574,7 +622,7 @@ void decommit_fri_batch(size_t num_queries, size_t max_index, const std::vector<
 // on the device and checked against `fri_layers` (a mismatch panics: the
 // layers belong to another commit).
 void decommit_fri(size_t num_queries, size_t max_index, const std::vector<std::vector<FE>>& fri_layers,
-                  const std::vector<MerkleTree>& fri_merkles, FriChannel& channel);
+                  const std::vector<MerkleTree>& fri_merkles, FriChannel& channel, uint32_t grinding_bits = 0);
 
 // Checks a transcript (the messages fri_commit then decommit_fri appended to
 // Channel::proof).  The reference's fri_verify.rs:12-177 is a sketch (it
@@ -584,9 +632,12 @@ void decommit_fri(size_t num_queries, size_t max_index, const std::vector<std::v
 // authentication path must reach its layer root, every layer-k value must
 // be the fold of its parents, the last layer must hold the final constant.
 // Host-only (SHA-256 on the CPU); returns false on any mismatch.
+// grinding_bits > 0: an 8-byte nonce must follow the final value and the state
+// after its send must have that many leading zero bits (the nonce need not be
+// the smallest); above 32 it panics.
 bool verify_fri(const std::vector<std::vector<uint8_t>>& messages, uint32_t log_n, size_t n_layers,
                 size_t num_queries, size_t max_index, FE offset = FE(FRI_GENERATOR),
-                const std::string& channel_state = "");
+                const std::string& channel_state = "", uint32_t grinding_bits = 0);
 
 // ------------------------------------------------ prover slice (configs[3])
 // src/prover, src/trace and src/composition are empty in the reference; the
@@ -607,7 +658,7 @@ struct StarkProof {
 };
 std::vector<FE> fibsq_trace(FE a1, uint32_t log_t);
 StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_queries, FriChannel& channel,
-                       FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr);
+                       FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr, uint32_t grinding_bits = 0);
 // prove_fibsq for many proofs of one shape, proof i with its own a1[i] and
 // channels[i], in a fixed number of device calls: one fri_trace_commit_batch,
 // one fri_fibsq_composition_commit_batch and one fri_batch_query_round per
@@ -622,7 +673,7 @@ StarkProof prove_fibsq(FE a1, uint32_t log_t, uint32_t log_blowup, size_t num_qu
 std::vector<StarkProof> prove_fibsq_batch(const std::vector<FE>& a1, uint32_t log_t, uint32_t log_blowup,
                                           size_t num_queries, std::vector<FriChannel>& channels,
                                           FE offset = FE(FRI_GENERATOR), std::shared_ptr<Gpu> gpu = nullptr,
-                                          bool device_queries = false);
+                                          bool device_queries = false, uint32_t grinding_bits = 0);
 // CP(x) from f(x), f(gx), f(g^2 x): what layer 0 must hold at a query.
 FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alphas, FE a_last, uint32_t log_t);
 // Verifier of prove_fibsq's transcript: replays the channel, checks the
@@ -630,7 +681,7 @@ FE fibsq_composition_at(FE f0, FE f1, FE f2, FE x, const std::array<FE, 3>& alph
 // every query, then every check of verify_fri.  Host-only.
 bool verify_fibsq(const std::vector<std::vector<uint8_t>>& messages, FE a_last, uint32_t log_t, uint32_t log_blowup,
                   size_t num_queries, size_t n_layers, FE offset = FE(FRI_GENERATOR),
-                  const std::string& channel_state = "");
+                  const std::string& channel_state = "", uint32_t grinding_bits = 0);
 
 // verify_fri / verify_fibsq for many transcripts of one shape in ONE device
 // call (fri_verify_batch, include/fri_amd.h: one kernel replays every channel,

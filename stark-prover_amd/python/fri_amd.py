@@ -59,6 +59,13 @@ MP_SMALL_LEAF = 4         # FRI_MP_SMALL_LEAF: leaf subtrees of 64 points
 MP_EVAL_MIN = 65536       # FRI_MP_EVAL_MIN: evaluation takes the tree from min(d, count) >= this
 MP_INTERP_MIN = 65536     # FRI_MP_INTERP_MIN: arbitrary-point interpolation takes the tree from n >= this
 VERIFY_MAX_QUERIES = 1024   # FRI_VERIFY_MAX_QUERIES: queries per member of fri_verify_batch
+GRIND_MAX_BITS = 32         # fri_grind: leading zero bits of the state after the nonce's send
+# The provers grind on the host (hashlib) below this many bits and on the
+# device (fri_grind / fri_grind_batch) from it up: the smallest measured size
+# from which the whole device call, about 32 us with its launches, read-back
+# and copies, beats the hashlib loop (78.6 us at 8 bits, 11.5 at 6;
+# profiles/grind.txt, table (v), rows 6 and 8, from tools/grind_probe.py)
+GRIND_DEVICE_MIN_BITS = 8
 # FRI_VERIFY_*: the verdict bits of fri_verify_batch (0 = accepted)
 VERIFY_CHANNEL, VERIFY_TRACE_PATH, VERIFY_COMPOSITION, VERIFY_FRI_PATH = 1, 2, 4, 8
 VERIFY_FOLD, VERIFY_FINAL, VERIFY_MALFORMED = 16, 32, 64
@@ -217,6 +224,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                         ctypes.POINTER(ctypes.c_uint64), pu32, sz, ctypes.POINTER(ctypes.c_uint8), sz,
                                         ctypes.POINTER(sz)]),
         "fri_debug_set_query_chunk": (i32, [vp, u32]),
+        "fri_grind": (i32, [vp, ctypes.POINTER(ChannelState), u32, ctypes.c_uint64, ctypes.c_uint64,
+                            ctypes.POINTER(ctypes.c_uint64), pu32, ctypes.POINTER(ChannelState)]),
+        "fri_grind_batch": (i32, [vp, u32, ctypes.POINTER(ChannelState), u32, ctypes.c_uint64,
+                                  ctypes.POINTER(ctypes.c_uint64), pu32]),
+        "fri_debug_set_grind_window": (i32, [vp, u32]),
         "fri_debug_transport_log": (i32, [vp, ctypes.POINTER(TransportOp), sz, ctypes.POINTER(sz)]),
         "fri_verify_batch": (i32, [vp, ctypes.POINTER(VerifyShape), u32, ctypes.POINTER(ChannelState), pu32, pu32,
                                    pu32, sz, ctypes.POINTER(ctypes.c_uint64), pu32, sz,
@@ -801,6 +813,50 @@ class Context:
         batch_query_phase calls (0: chosen by the staging budget)."""
         self._check(self.lib.fri_debug_set_query_chunk(self.h, members))
 
+    def grind(self, state: Optional[bytes], bits: int, first: int = 0, last: int = 2 ** 64 - 1):
+        """fri_grind: the smallest nonce in [first, last] whose 8-byte send
+        leaves the channel with ``bits`` leading zero bits.  ``state``: the
+        32 digest bytes of the channel before the send, or None for an empty
+        state.  Returns (nonce, state after the send), or None when the range
+        holds no such nonce."""
+        if bits < 0 or first < 0 or last < 0 or bits >> 32 or first >> 64 or last >> 64:
+            raise FriError(FRI_EINVAL, "bits, first and last must be non-negative (32 and 64 bits)")
+        cin, cout = ChannelState(), ChannelState()
+        if state:
+            if len(state) != 32:
+                raise FriError(FRI_EINVAL, "a channel state is 32 digest bytes or None")
+            ctypes.memmove(cin.digest, bytes(state), 32)
+            cin.has_state = 1
+        nonce, found = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._check(self.lib.fri_grind(self.h, ctypes.byref(cin), bits, first, last, ctypes.byref(nonce),
+                                       ctypes.byref(found), ctypes.byref(cout)))
+        return (int(nonce.value), bytes(cout.digest)) if found.value else None
+
+    def grind_batch(self, states, bits: int, last: int = 2 ** 64 - 1):
+        """fri_grind_batch: Context.grind from 0 for every member of
+        ``states`` (32 digest bytes, or None for an empty state) in shared
+        launches.  Returns one (nonce, state after the send) or None per
+        member."""
+        batch = len(states)
+        if bits < 0 or last < 0 or bits >> 32 or last >> 64:
+            raise FriError(FRI_EINVAL, "bits and last must be non-negative (32 and 64 bits)")
+        chs = (ChannelState * max(batch, 1))()
+        for b, st in enumerate(states):
+            if st:
+                if len(st) != 32:
+                    raise FriError(FRI_EINVAL, "a channel state is 32 digest bytes or None")
+                ctypes.memmove(chs[b].digest, bytes(st), 32)
+                chs[b].has_state = 1
+        nonces = (ctypes.c_uint64 * max(batch, 1))()
+        found = (ctypes.c_uint32 * max(batch, 1))()
+        self._check(self.lib.fri_grind_batch(self.h, batch, chs, bits, last, nonces, found))
+        return [(int(nonces[b]), bytes(chs[b].digest)) if found[b] else None for b in range(batch)]
+
+    def set_grind_window(self, log_window: int):
+        """fri_debug_set_grind_window: log2 of the nonces per launch of later
+        grind / grind_batch calls (1..32; 0: chosen from ``bits``)."""
+        self._check(self.lib.fri_debug_set_grind_window(self.h, log_window))
+
     def verify_batch(self, shape: "VerifyShape", batch: int, chan, n_layers, a_last, head, head_stride: int,
                      indices, values, values_stride: int, paths, paths_stride: int, verdict=None) -> np.ndarray:
         """fri_verify_batch over the raw ABI: ``shape`` a VerifyShape, ``chan``
@@ -1148,6 +1204,12 @@ def plan_layout(d: int, log_n: int, world: int = 1, rank: int = 0) -> dict:
 # ----------------------------------------------------------------------------
 # Reference-shaped host objects
 # ----------------------------------------------------------------------------
+def state_has_zero_bits(state: str, bits: int) -> bool:
+    """The grinding check: the ``bits`` most significant bits of a channel
+    state (64 hex characters) are zero."""
+    return len(state) == 64 and int(state, 16) >> (256 - bits) == 0
+
+
 @dataclass
 class Channel:
     """src/channel/channel.rs — host-side transcript (authoritative state).
@@ -1197,6 +1259,34 @@ class Channel:
             if i % per:
                 self.compressed_proof.append(bytes(m))
         self.state = state
+
+    def grind(self, bits: int, ctx: Optional["Context"] = None, first: int = 0) -> int:
+        """Proof of work before the query phase (fri_amd.h, fri_grind): finds
+        the smallest nonce >= ``first`` whose send leaves the state with
+        ``bits`` leading zero bits (0..32), sends it as an 8-byte message and
+        returns it.  Without ``ctx`` the search is a host loop (hashlib), with
+        one it runs on the device; the send and the check of the new state are
+        the host's either way.  FriError when no nonce up to 2^64 - 1 does."""
+        if not 0 <= bits <= GRIND_MAX_BITS or not 0 <= first < 1 << 64:
+            raise FriError(FRI_EINVAL, "bits must be 0..32 and first below 2^64")
+        nonce = None
+        if ctx is None:
+            head = hashlib.sha256(self.state.encode())
+            for v in range(first, 1 << 64):
+                h = head.copy()
+                h.update(b"%016x" % v)
+                if int.from_bytes(h.digest()[:4], "big") >> (32 - bits) == 0:
+                    nonce = v
+                    break
+        else:
+            got = ctx.grind(bytes.fromhex(self.state) if self.state else None, bits, first)
+            nonce = got[0] if got else None
+        if nonce is None:
+            raise FriError(FRI_ESTATE, "no nonce in range gives the state the zero bits")
+        self.send(nonce.to_bytes(8, "big"))
+        if not state_has_zero_bits(self.state, bits):
+            raise FriError(FRI_ESTATE, "the state after the nonce lacks the zero bits")
+        return nonce
 
     def proof_size(self) -> int:                                         # channel.rs:88-90
         return sum(len(b) for b in self.proof)
@@ -1342,15 +1432,51 @@ def _send_openings(openings, channel: Channel) -> None:
         channel.send(spath)
 
 
-def decommit_fri(num_queries: int, max_index: int, proof, merkles_or_channel, channel: Optional[Channel] = None) -> None:
+def _check_grinding_bits(bits: int) -> None:
+    if not 0 <= bits <= GRIND_MAX_BITS:
+        raise FriError(FRI_EINVAL, "grinding_bits must be 0..32")
+
+
+def _grind(channel: Channel, bits: int, ctx: "Context") -> None:
+    """A prover's grinding step: nothing for 0 bits, else Channel.grind, on
+    the host below GRIND_DEVICE_MIN_BITS and on ``ctx`` from it up."""
+    _check_grinding_bits(bits)
+    if bits:
+        channel.grind(bits, ctx if bits >= GRIND_DEVICE_MIN_BITS else None)
+
+
+def _grind_batch(channels: Sequence[Channel], bits: int, ctx: "Context") -> None:
+    """_grind for every member's channel; on the device it is ONE
+    fri_grind_batch on the members' states, and every channel then sends its
+    nonce and must arrive at the state the device returned."""
+    _check_grinding_bits(bits)
+    if not bits:
+        return
+    if bits < GRIND_DEVICE_MIN_BITS:
+        for ch in channels:
+            ch.grind(bits)
+        return
+    got = ctx.grind_batch([bytes.fromhex(ch.state) if ch.state else None for ch in channels], bits)
+    for b, (ch, g) in enumerate(zip(channels, got)):
+        if g is None:
+            raise FriError(FRI_ESTATE, f"member {b}: no nonce in range gives the state the zero bits")
+        ch.send(g[0].to_bytes(8, "big"))
+        if ch.state != g[1].hex() or not state_has_zero_bits(ch.state, bits):
+            raise FriError(FRI_ESTATE, f"member {b}: the state after the nonce is not the device's")
+
+
+def decommit_fri(num_queries: int, max_index: int, proof, merkles_or_channel, channel: Optional[Channel] = None,
+                 grinding_bits: int = 0) -> None:
     """src/fri/fri_commit.rs:168-179: each index drawn with
     receive_random_int(0, max_index, true) from the transcript so far.
     Two forms: decommit_fri(q, max, proof, channel), or the reference's own
     decommit_fri(q, max, fri_layers, fri_merkles, channel) with the proof's
     ``fri_layers`` and device-backed ``fri_merkles`` (the commit is found
     through the trees; their generation must still be resident, and the
-    openings must equal ``fri_layers``)."""
+    openings must equal ``fri_layers``).  ``grinding_bits`` > 0: the channel
+    first grinds that many bits (Channel.grind; fri_amd.h, fri_grind)."""
     if channel is None:
+        _grind(merkles_or_channel, grinding_bits, proof.ctx.ctx if isinstance(proof.ctx, BatchMember) else proof.ctx)
         for _ in range(num_queries):
             idx = merkles_or_channel.receive_random_int(0, max_index, True)
             decommit_fri_layers(idx, proof, merkles_or_channel)
@@ -1363,6 +1489,7 @@ def decommit_fri(num_queries: int, max_index: int, proof, merkles_or_channel, ch
                                      for k, t in enumerate(merkles)):
         raise FriError(FRI_EINVAL, "fri_merkles are not the device-backed trees of one commit")
     ctx, log_n = t0._ctx, t0._log_n
+    _grind(channel, grinding_bits, ctx.ctx if isinstance(ctx, BatchMember) else ctx)
     for _ in range(num_queries):
         idx = channel.receive_random_int(0, max_index, True)
         openings = ctx.decommit_query(idx, len(merkles), log_n, t0._generation, t0._sharded)
@@ -1386,7 +1513,7 @@ def _merkle_path_ok(value: int, index: int, path: bytes, depth: int, root: bytes
 
 
 def verify_fri(messages: Sequence[bytes], log_n: int, n_layers: int, num_queries: int, max_index: int,
-               offset: int = GENERATOR, channel_state: str = "") -> bool:
+               offset: int = GENERATOR, channel_state: str = "", grinding_bits: int = 0) -> bool:
     """Check a FRI transcript: the proof messages that fri_commit followed by
     decommit_fri append to Channel.proof (fri_commit.rs:72-179).
 
@@ -1402,8 +1529,12 @@ def verify_fri(messages: Sequence[bytes], log_n: int, n_layers: int, num_queries
       * the last layer must hold the final constant.
     ``n_layers`` = number of committed layers (the reference's
     expected_num_layers). Returns False on any mismatch or malformed transcript.
+    ``grinding_bits`` > 0: an 8-byte nonce must follow the final value, and
+    the state after its send must have that many leading zero bits (the
+    nonce need not be the smallest).
     """
-    return _verify_transcript(messages, log_n, n_layers, num_queries, max_index, offset, channel_state)
+    return _verify_transcript(messages, log_n, n_layers, num_queries, max_index, offset, channel_state,
+                              grinding_bits=grinding_bits)
 
 
 class _Reject(Exception):
@@ -1411,11 +1542,12 @@ class _Reject(Exception):
 
 
 def _verify_transcript(messages, log_n, n_layers, num_queries, max_index, offset, channel_state,
-                       pre_commit=None, on_query=None) -> bool:
+                       pre_commit=None, on_query=None, grinding_bits=0) -> bool:
     """verify_fri's replay with two hooks for a STARK around the FRI:
     ``pre_commit(take, ch)`` consumes the messages before the first FRI root;
     ``on_query(take, ch, idx)`` those between a query index and its layer
     openings, and returns the value layer 0 must hold at idx (or None)."""
+    _check_grinding_bits(grinding_bits)
     msgs = list(messages)
     pos = 0
 
@@ -1447,6 +1579,13 @@ def _verify_transcript(messages, log_n, n_layers, num_queries, max_index, offset
             return False
         final = int.from_bytes(fin, "big")
         ch.send(fin)
+        if grinding_bits:
+            nonce = take()
+            if len(nonce) != 8:
+                return False
+            ch.send(nonce)
+            if not state_has_zero_bits(ch.state, grinding_bits):
+                return False
         inv2 = pow(2, P - 2, P)
         for _ in range(num_queries):
             idx = ch.receive_random_int(0, max_index, True)
@@ -1520,13 +1659,16 @@ class StarkProof:
 
 
 def prove_fibsq(a1: int, log_t: int, log_blowup: int, num_queries: int, channel: Channel,
-                offset: int = GENERATOR, ctx: Optional[Context] = None) -> StarkProof:
+                offset: int = GENERATOR, ctx: Optional[Context] = None, grinding_bits: int = 0) -> StarkProof:
     """STARK-101 prover on the GPU: trace -> LDE + Merkle (fri_trace_commit),
     send the trace root, draw alpha_0..2, composition polynomial + FRI commit
     (fri_fibsq_composition_commit), then per query (index drawn with
     receive_random_int(0, n - 2B - 1, true)) send f(x), f(gx), f(g^2 x) with
     their paths and the FRI layer openings (decommit_fri_layers,
-    fri_commit.rs:137-163).  The transcript is ``channel.proof``."""
+    fri_commit.rs:137-163).  The transcript is ``channel.proof``.
+    ``grinding_bits`` > 0: between the FRI commit's final value and the
+    first query index the channel grinds that many bits (Channel.grind)."""
+    _check_grinding_bits(grinding_bits)
     L = log_t + log_blowup
     B, n = 1 << log_blowup, 1 << L
     ctx = ctx or _default_ctx(L)
@@ -1537,6 +1679,7 @@ def prove_fibsq(a1: int, log_t: int, log_blowup: int, num_queries: int, channel:
     res = ctx.fibsq_composition_commit(log_t, log_blowup, int(trace[-1]), alphas, offset,
                                        channel_state=bytes.fromhex(channel.state))
     fri = _mirror_commit(res, ctx, L, channel)
+    _grind(channel, grinding_bits, ctx)
     queries = []
     for _ in range(num_queries):
         idx = channel.receive_random_int(0, n - 2 * B - 1, True)
@@ -1561,12 +1704,12 @@ def fibsq_cp_at(f0: int, f1: int, f2: int, x: int, alphas: Sequence[int], a_last
 
 
 def verify_fibsq(messages: Sequence[bytes], a_last: int, log_t: int, log_blowup: int, num_queries: int,
-                 n_layers: int, offset: int = GENERATOR, channel_state: str = "") -> bool:
+                 n_layers: int, offset: int = GENERATOR, channel_state: str = "", grinding_bits: int = 0) -> bool:
     """Verifier of prove_fibsq's transcript: replays the channel (trace root,
     alphas, FRI roots/betas/final, query indices), checks every trace path
     against the trace root, that layer 0 at each query equals the composition
     polynomial computed from the opened f(x), f(gx), f(g^2 x), and then every
-    FRI check of verify_fri."""
+    FRI check of verify_fri, the nonce of ``grinding_bits`` > 0 included."""
     L = log_t + log_blowup
     B, n = 1 << log_blowup, 1 << L
     a_last = int(a_last)
@@ -1600,7 +1743,7 @@ def verify_fibsq(messages: Sequence[bytes], a_last: int, log_t: int, log_blowup:
         return fibsq_cp_at(fs[0], fs[1], fs[2], x, state["alphas"], a_last, log_t)
 
     return _verify_transcript(messages, L, n_layers, num_queries, n - 2 * B - 1, offset, channel_state,
-                              pre_commit, on_query)
+                              pre_commit, on_query, grinding_bits)
 
 
 _CTX_CACHE = {}
@@ -1864,7 +2007,7 @@ def _device_query_phase(ctx: "Context", num_queries: int, max_index: int, fris: 
 
 
 def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIProof"],
-                       channels: Sequence[Channel], device_queries: bool = False) -> None:
+                       channels: Sequence[Channel], device_queries: bool = False, grinding_bits: int = 0) -> None:
     """decommit_fri (fri_commit.rs:168-179) for every member of one batch
     (``proofs`` as fri_commit_batch or prove_fibsq_batch returned them, in
     member order): per round every channel draws its index, ONE
@@ -1876,7 +2019,11 @@ def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIPr
     with 8 and 32 queries, blowup 8): the whole call is slower than the round
     route at B = 16 (0.47x to 0.71x) and faster from B = 64, the smallest
     measured size where it wins, at every shape and in both runs (1.1x to
-    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096)."""
+    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096).
+    ``grinding_bits`` > 0: every channel first grinds that many bits, on the
+    device in ONE fri_grind_batch from GRIND_DEVICE_MIN_BITS up, by either
+    route."""
+    _check_grinding_bits(grinding_bits)
     if len(proofs) != len(channels):
         raise FriError(FRI_EINVAL, "one channel per proof")
     if len(proofs) == 0:
@@ -1888,6 +2035,7 @@ def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIPr
     g, members, ln = ctx.batch_info()
     if g != gen or members != len(proofs) or ln != log_n:
         raise FriError(FRI_ESTATE, "FRIProof layers were replaced by a later commit on the same context")
+    _grind_batch(channels, grinding_bits, ctx)
     if device_queries:
         _device_query_phase(ctx, num_queries, max_index, proofs, channels, log_n, 0, 0)
         return
@@ -1900,7 +2048,7 @@ def decommit_fri_batch(num_queries: int, max_index: int, proofs: Sequence["FRIPr
 
 def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queries: int, channels: Sequence[Channel],
                       offset: int = GENERATOR, ctx: Optional[Context] = None,
-                      device_queries: bool = False) -> List[StarkProof]:
+                      device_queries: bool = False, grinding_bits: int = 0) -> List[StarkProof]:
     """prove_fibsq for many proofs of one shape, each with its own a1 and
     channel, in a fixed number of device calls: one fri_trace_commit_batch,
     one fri_fibsq_composition_commit_batch and one fri_batch_query_round per
@@ -1914,7 +2062,12 @@ def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queri
     with 8 and 32 queries, blowup 8): the whole call is slower than the round
     route at B = 16 (0.47x to 0.71x) and faster from B = 64, the smallest
     measured size where it wins, at every shape and in both runs (1.1x to
-    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096)."""
+    1.5x at 64, 1.9x to 2.5x at 256, up to 3.0x at 4096).
+    ``grinding_bits`` > 0: after the composition commit every channel grinds
+    that many bits, on the device in ONE fri_grind_batch from
+    GRIND_DEVICE_MIN_BITS up, by either route; the device route's query phase
+    starts from the states that call returned."""
+    _check_grinding_bits(grinding_bits)
     if len(a1s) != len(channels):
         raise FriError(FRI_EINVAL, "one channel per proof")
     if len(a1s) == 0:
@@ -1936,6 +2089,7 @@ def prove_fibsq_batch(a1s: Sequence[int], log_t: int, log_blowup: int, num_queri
         fri = _mirror_commit(r, BatchMember(ctx, b), L, ch, generation=gen)
         fri.member = b
         fris.append(fri)
+    _grind_batch(channels, grinding_bits, ctx)
     queries = [[] for _ in a1s]
     if device_queries:
         queries = _device_query_phase(ctx, num_queries, n - 2 * B - 1, fris, channels, L, 3, B)
