@@ -2,7 +2,7 @@
 // (device only).  Frozen spec: a message is hex-encoded before
 // it is hashed (channel.rs:35-44), so 4 bytes become 2 big-endian message
 // words, and a root, which is sent as its own hex, is hex-encoded twice.
-// Shared by the commit's channel wave (fri_layer.hip) and the batched
+// Shared by the commit's channel wave (fri_tree_device.hpp) and the batched
 // verifier's channel replay (fri_verify_kernels.hip).
 #pragma once
 #include <stdint.h>

@@ -1,7 +1,7 @@
 // fri_batch.hip — fri_commit_batch: B independent commits of one shape
 // (src/fri/fri_commit.rs:72-122 each) in one call.  The LDE of every member
 // is a fixed number of launches, then ONE launch commits them all, one
-// workgroup per member (k_commit_batch, fri_layer.hip).  The batch has its
+// workgroup per member (k_commit_batch, fri_batch_kernels.hip).  The batch has its
 // own buffers (Batch, fri_host.hpp): no lane's plan or graph is touched, so a
 // single commit afterwards replays what it captured.  The member-wise
 // read-backs are fri_readback.hip's.  Below the commit the batched prover:

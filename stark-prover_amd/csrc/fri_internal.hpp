@@ -275,7 +275,7 @@ void launch_replicate(const uint32_t* src, uint32_t* dst, size_t words, uint32_t
 // nodes, <= 512) is already in t.tree; mx/G: coefficient maxima.
 void launch_top(const LayerTask& t, uint32_t l, const int32_t* mx, uint32_t G, hipStream_t s);
 
-// Batched commit (fri_commit_batch; k_commit_batch, fri_layer.hip): `batch`
+// Batched commit (fri_commit_batch; k_commit_batch, fri_batch_kernels.hip): `batch`
 // independent commits of one shape, one 512-thread workgroup each.  Member b
 // owns the slice b of every buffer (layers + b * lay_stride, ...), laid out
 // inside like a one-GPU plan (layer_off / tree_off, in words); the x^-1 tables
