@@ -751,6 +751,18 @@ int fri_debug_set_grind_window(fri_ctx* ctx, uint32_t log_window);   /* nonces p
  * fri_decommit_query's layout).  chan_in[b]: the channel before the member's
  * first message.
  *
+ * Grinding (fri_verify_batch_pow).  With grinding_bits > 0 every transcript
+ * carries the 8-byte nonce a prover route sends after the final value and
+ * before the first query index (fri_grind above); member b's is nonces[b], a
+ * plain host uint64_t: the array fri_grind_batch writes feeds this call
+ * without repacking, like the query records.  The channel kernel sends it
+ * after the final value, and the state after that send must have grinding_bits
+ * leading zero bits, else FRI_VERIFY_POW.  The replay goes on from that state
+ * whether it has them or not, so a transcript that only lacks bits gets
+ * FRI_VERIFY_POW and nothing else.  The nonce need not be the smallest.  With
+ * grinding_bits = 0 there is no such message, nonces is not read and may be
+ * NULL: fri_verify_batch is fri_verify_batch_pow(..., 0, NULL, verdict).
+ *
  * Numbers taken from a transcript only choose left/right in a path climb and
  * exponents of domain points (indices are taken mod the layer size, trace
  * positions mod 2^log_n); they never form an address.
@@ -758,8 +770,8 @@ int fri_debug_set_grind_window(fri_ctx* ctx, uint32_t log_window);   /* nonces p
  * FRI_EINVAL, with nothing written: a shape outside the limits in
  * fri_verify_shape, strides below the record's size, batch outside 1..65535,
  * n_layers[b] outside 1..max_layers, offset or a_last[b] >= p, a multi-GPU
- * context.  FRI_ENOMEM (one member's staging does not fit) leaves the context
- * usable.  Otherwise FRI_OK, whatever the verdicts.  The members are uploaded
+ * context, grinding_bits > 32, grinding_bits > 0 with nonces = NULL.
+ * FRI_ENOMEM (one member's staging does not fit) leaves the context usable.  Otherwise FRI_OK, whatever the verdicts.  The members are uploaded
  * and checked in chunks of a 2 GiB staging budget, one launch pair each
  * (fri_debug_set_verify_chunk: members per chunk, 0 = by the budget); the
  * staging belongs to the context and stays until fri_ctx_destroy.  The two
@@ -775,7 +787,12 @@ int fri_debug_set_grind_window(fri_ctx* ctx, uint32_t log_window);   /* nonces p
  * queries 591 at B = 16, 31.2 at 256 and 2.6 at 4096 against 308 / 22.0; at log_t 13
  * with 32 queries 5162, 244 and 21.1 against 2367 / 152.  One lane hashes a whole
  * transcript, so the channel kernel runs for milliseconds whatever the batch: the
- * call loses to one core below B = 64 and to 16 threads below B = 4096. */
+ * call loses to one core below B = 64 and to 16 threads below B = 4096.
+ * The nonce (profiles/verify_batch_pow.txt): fri_verify_batch is as fast as
+ * before it existed (the kernel without bits is the same instructions), and
+ * fri_verify_batch_pow with 8 bits costs 0.32 us per proof more at log_t 7,
+ * 8 queries, B = 256 (1.0%), 0.019 at B = 4096, 1.85 at log_t 13, 32 queries,
+ * B = 256 and 0.12 at B = 4096 (0.6%). */
 #define FRI_VERIFY_MAX_QUERIES 1024
 #define FRI_VERIFY_CHANNEL      1u   /* a claimed alpha, beta or query index is not what the replayed channel draws */
 #define FRI_VERIFY_TRACE_PATH   2u   /* a trace opening does not reach the trace root                               */
@@ -784,6 +801,7 @@ int fri_debug_set_grind_window(fri_ctx* ctx, uint32_t log_window);   /* nonces p
 #define FRI_VERIFY_FOLD        16u   /* a layer-k value is not the fold of its layer-(k-1) pair                    */
 #define FRI_VERIFY_FINAL       32u   /* the last layer's pair is not the final value                               */
 #define FRI_VERIFY_MALFORMED   64u   /* a packed word >= p, or (set by the host mirrors) a transcript that cannot be packed */
+#define FRI_VERIFY_POW        128u   /* the state after the nonce's send lacks grinding_bits leading zero bits     */
 typedef struct {
     uint32_t log_n;        /* layer 0 has 2^log_n values; 1..min(30, ctx log_n_max) */
     uint32_t max_layers;   /* record stride in layers, 1..log_n+1                   */
@@ -805,6 +823,13 @@ int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uint32_t batch
                      const uint32_t* values, size_t values_stride,  /* words per (member, query) */
                      const uint8_t* paths, size_t paths_stride,     /* bytes per (member, query) */
                      uint32_t* verdict);                             /* [batch] mask, 0 = accepted */
+int fri_verify_batch_pow(fri_ctx* ctx, const fri_verify_shape* shape, uint32_t batch,
+                         const fri_channel_state* chan_in, const uint32_t* n_layers, const uint32_t* a_last,
+                         const uint32_t* head, size_t head_stride, const uint64_t* indices,
+                         const uint32_t* values, size_t values_stride, const uint8_t* paths, size_t paths_stride,
+                         uint32_t grinding_bits,            /* 0..32; 0: no nonce message */
+                         const uint64_t* nonces,            /* [batch] when grinding_bits > 0, else ignored */
+                         uint32_t* verdict);
 int fri_debug_set_verify_chunk(fri_ctx* ctx, uint32_t members);    /* 0 = automatic */
 
 /* Which commit the read-backs below serve: `generation` grows with every

@@ -2,7 +2,8 @@
 // (tools/batch_probe.py --verify runs it): the baselines of the batched
 // verifier and the mirror's whole call.
 //   make -C stark-prover_amd verify_native
-//   build/verify_native [log_t=7] [log_blowup=3] [queries=8] [batch=256] [reps=5] [threads=16]
+//   build/verify_native [log_t=7] [log_blowup=3] [queries=8] [batch=256] [reps=5] [threads=16] [grinding_bits=0]
+// Proves (and verifies) with `grinding_bits` bits of proof of work.
 // Proves min(batch, 256) members once and repeats them up to `batch`, then
 // prints one JSON object with the medians, in microseconds per proof:
 //   loop_1      a loop of verify_fibsq on one core (over min(batch, 256) members)
@@ -40,13 +41,14 @@ int main(int argc, char** argv) {
     const size_t B = argc > 4 ? static_cast<size_t>(std::atoi(argv[4])) : 256;
     const int reps = argc > 5 ? std::atoi(argv[5]) : 5;
     const unsigned threads = argc > 6 ? static_cast<unsigned>(std::atoi(argv[6])) : 16;
+    const uint32_t bits = argc > 7 ? static_cast<uint32_t>(std::atoi(argv[7])) : 0;
     try {
         auto gpu = std::make_shared<Gpu>(0, std::max<uint32_t>(12, log_t + lb));
         const size_t m = std::min<size_t>(B, 256);
         std::vector<FE> a1;
         for (size_t b = 0; b < m; b++) a1.push_back(FE(1000003 * b + 3141592));
         std::vector<FriChannel> ch(m);
-        const auto proofs = prove_fibsq_batch(a1, log_t, lb, q, ch, FE(FRI_GENERATOR), gpu);
+        const auto proofs = prove_fibsq_batch(a1, log_t, lb, q, ch, FE(FRI_GENERATOR), gpu, false, bits);
         std::vector<Msgs> t;
         std::vector<FE> a_last;
         std::vector<size_t> nl;
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
         std::atomic<size_t> accepted{0};
         auto loop = [&](size_t lo, size_t hi) {
             size_t ok = 0;
-            for (size_t b = lo; b < hi; b++) ok += verify_fibsq(t[b], a_last[b], log_t, lb, q, nl[b]);
+            for (size_t b = lo; b < hi; b++) ok += verify_fibsq(t[b], a_last[b], log_t, lb, q, nl[b], FE(FRI_GENERATOR), "", bits);
             accepted += ok;
         };
         const double loop_1 = median_us([&] { loop(0, m); }, reps, m);
@@ -70,9 +72,9 @@ int main(int argc, char** argv) {
             },
             reps, m);
         bool ok = accepted == 2 * static_cast<size_t>(reps) * m;
-        std::vector<bool> got = verify_fibsq_batch(t, a_last, log_t, lb, q, nl, FE(FRI_GENERATOR), {}, gpu);   // warm
+        std::vector<bool> got = verify_fibsq_batch(t, a_last, log_t, lb, q, nl, FE(FRI_GENERATOR), {}, gpu, nullptr, bits);   // warm
         const double whole = median_us(
-            [&] { got = verify_fibsq_batch(t, a_last, log_t, lb, q, nl, FE(FRI_GENERATOR), {}, gpu); }, reps, B);
+            [&] { got = verify_fibsq_batch(t, a_last, log_t, lb, q, nl, FE(FRI_GENERATOR), {}, gpu, nullptr, bits); }, reps, B);
         for (bool g : got) ok = ok && g;
         std::printf("{\"loop_1\": %.2f, \"loop_n\": %.2f, \"batch_whole\": %.2f, \"threads\": %u, \"batch\": %zu, "
                     "\"accepted\": %s}\n",

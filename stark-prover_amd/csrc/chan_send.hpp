@@ -95,14 +95,15 @@ enum : uint32_t { MSG_PATH = 0, MSG_ROOT = 1, MSG_VALUE = 2 };
 //              rehash (channel.rs:75-76), sha256(hex(cs));
 //   MSG_ROOT   the root's 64-character hex, hex-encoded again: two blocks of
 //              hexhex from the 8 digest words of src, then the padding block;
-//   MSG_VALUE  the 8 bytes be64(v): 16 hex characters and the padding in one
-//              block.
+//   MSG_VALUE  the 8 bytes be64(vhi * 2^32 + v): 16 hex characters and the
+//              padding in one block (vhi is 0 for a field element and a query
+//              index; a grinding nonce is a full 64-bit number).
 // kind and nd are wave-uniform; `has` and src are the lane's.  The next node
 // is in flight under the current block's rounds.  The ONE call site of
 // compress_c in a chain kernel.
 template <class Src>
 __device__ __forceinline__ void chan_send(uint32_t cs[8], uint32_t& has, uint32_t kind, const Src& src, uint32_t nd,
-                                          uint32_t v) {
+                                          uint32_t v, uint32_t vhi) {
     uint32_t X[8], nxt[8];
     sha::init(X);
     if (kind == MSG_PATH && nd) src.node(0u, nxt);
@@ -133,7 +134,7 @@ __device__ __forceinline__ void chan_send(uint32_t cs[8], uint32_t& has, uint32_
 #pragma unroll
             for (int j = 0; j < 16; j++) w[j] = 0u;
             if (kind == MSG_VALUE) {
-                w[0] = 0x30303030u; w[1] = 0x30303030u;   // "00000000": the u64's high word is 0
+                hex2(vhi, w[0], w[1]);                    // "00000000" where the u64's high word is 0
                 hex2(v, w[2], w[3]);
                 w[4] = 0x80000000u;
             } else {

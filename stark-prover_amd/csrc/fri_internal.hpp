@@ -415,14 +415,14 @@ void launch_grind_prep(const uint32_t* chan, GrindMember* mem, unsigned long lon
                        hipStream_t s);
 void launch_grind(const GrindTask& q, hipStream_t s);
 
-// fri_verify_kernels.hip — the batched verifier (fri_verify_batch): `members`
+// fri_verify_kernels.hip — the batched verifier (fri_verify_batch_pow): `members`
 // transcripts of one shape, packed as fri_amd.h describes, in device memory
 // with compact strides.  Both kernels OR what they find into verdict[b]
 // (FRI_VERIFY_* bits); neither reads what the other writes.
 constexpr uint32_t VERIFY_MAX_LOG = 30;
 enum : uint32_t {                // FRI_VERIFY_* of fri_amd.h (fri_verify.hip asserts they agree)
     VB_CHANNEL = 1, VB_TRACE_PATH = 2, VB_COMPOSITION = 4, VB_FRI_PATH = 8, VB_FOLD = 16, VB_FINAL = 32,
-    VB_MALFORMED = 64
+    VB_MALFORMED = 64, VB_POW = 128
 };
 struct VerifyTask {
     const uint32_t* head;        // per member: [trace root 8, alphas 3] roots 8 * max_layers, betas, final
@@ -439,6 +439,9 @@ struct VerifyTask {
     uint32_t glast_m, gprev_m;   // Montgomery(g^{T-1}), Montgomery(g^{T-2}), g = w_T (trace_count = 3)
     // Montgomery(w_{2^(log_n-k)}) and Montgomery(offset^(2^k)): layer k lives on offset^(2^k) <w_{2^(log_n-k)}>
     uint32_t w_m[VERIFY_MAX_LOG + 1], off_m[VERIFY_MAX_LOG + 1];
+    // the grinding nonce (fri_verify_batch_pow), behind everything else: the kernels without it keep their argument layout
+    const uint64_t* nonces;      // per member (pow_bits > 0; not read otherwise)
+    uint32_t pow_bits;           // grinding bits, 0..32: 0 = the transcripts carry no nonce
 };
 void launch_verify_chain(const VerifyTask& t, hipStream_t s);
 void launch_verify_open(const VerifyTask& t, hipStream_t s);

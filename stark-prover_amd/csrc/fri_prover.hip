@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void k_query_chain(QueryPhase q) {
                     else { src = TreeNodes{tre + q.tree_off[k], depth, leaf}; nd = depth; }
                 }
                 if (!act) continue;
-                chan_send(cs, has, kind, src, nd, v);
+                chan_send(cs, has, kind, src, nd, v, 0u);
             }
         }
     }

@@ -1,12 +1,13 @@
-// fri_verify.hip — the batched verifier's host side (fri_verify_batch,
-// include/fri_amd.h): argument checks, the staging buffer, the
+// fri_verify.hip — the batched verifier's host side (fri_verify_batch and
+// fri_verify_batch_pow, include/fri_amd.h): argument checks, the staging buffer, the
 // upload of a chunk of members and its launch pair (fri_verify_kernels.hip).
 // Reads and changes nothing of the resident commit, batch or trace batch.
 #include "fri_host.hpp"
 
 static_assert(VB_CHANNEL == FRI_VERIFY_CHANNEL && VB_TRACE_PATH == FRI_VERIFY_TRACE_PATH &&
                   VB_COMPOSITION == FRI_VERIFY_COMPOSITION && VB_FRI_PATH == FRI_VERIFY_FRI_PATH &&
-                  VB_FOLD == FRI_VERIFY_FOLD && VB_FINAL == FRI_VERIFY_FINAL && VB_MALFORMED == FRI_VERIFY_MALFORMED,
+                  VB_FOLD == FRI_VERIFY_FOLD && VB_FINAL == FRI_VERIFY_FINAL && VB_MALFORMED == FRI_VERIFY_MALFORMED &&
+                  VB_POW == FRI_VERIFY_POW,
               "verdict bits");
 static_assert(sizeof(fri_channel_state) == 36, "k_verify_chain reads a channel state as 9 words");
 
@@ -23,10 +24,11 @@ namespace {
 constexpr size_t VERIFY_CHUNK_BYTES = (size_t)2 << 30;   // staging budget of one launch pair (2 GiB)
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Sections of the staging buffer for m members (offsets in bytes)
+// Sections of the staging buffer for m members (offsets in bytes); the nonces
+// have one only with grinding bits, so without them the size is what it was
 struct Sections {
-    size_t head, chan, nl, alast, idx, vals, paths, verdict, total;
-    Sections(size_t m, size_t hw, size_t q, size_t vw, size_t pw) {
+    size_t head, chan, nl, alast, idx, vals, paths, verdict, nonce, total;
+    Sections(size_t m, size_t hw, size_t q, size_t vw, size_t pw, bool pow) {
         size_t o = 0;
         head = o;    o += al256(m * hw * 4);
         chan = o;    o += al256(m * sizeof(fri_channel_state));
@@ -36,6 +38,7 @@ struct Sections {
         vals = o;    o += al256(m * q * vw * 4);
         paths = o;   o += al256(m * q * pw * 4);
         verdict = o; o += al256(m * 4);
+        nonce = o;   o += pow ? al256(m * 8) : 0;
         total = o;
     }
 };
@@ -59,7 +62,20 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
                                 const uint32_t* head, size_t head_stride, const uint64_t* indices,
                                 const uint32_t* values, size_t values_stride, const uint8_t* paths,
                                 size_t paths_stride, uint32_t* verdict) {
+    return fri_verify_batch_pow(ctx, shape, batch, chan_in, n_layers, a_last, head, head_stride, indices, values,
+                                values_stride, paths, paths_stride, 0, nullptr, verdict);
+}
+
+extern "C" int fri_verify_batch_pow(fri_ctx* ctx, const fri_verify_shape* shape, uint32_t batch,
+                                    const fri_channel_state* chan_in, const uint32_t* n_layers,
+                                    const uint32_t* a_last, const uint32_t* head, size_t head_stride,
+                                    const uint64_t* indices, const uint32_t* values, size_t values_stride,
+                                    const uint8_t* paths, size_t paths_stride, uint32_t grinding_bits,
+                                    const uint64_t* nonces, uint32_t* verdict) {
     if (!ctx || !shape || !chan_in || !n_layers || !head || !verdict) return fail(ctx, FRI_EINVAL, "null argument");
+    if (grinding_bits > 32) return fail(ctx, FRI_EINVAL, "grinding_bits must be 0..32");
+    if (grinding_bits && !nonces) return fail(ctx, FRI_EINVAL, "null argument (nonces with grinding_bits > 0)");
+    const bool pow = grinding_bits != 0;
     if (ctx->team_root || ctx->tp.team)
         return fail(ctx, FRI_EINVAL, "multi-GPU context: the batched verifier runs on one-device contexts");
     const fri_verify_shape& sh = *shape;
@@ -101,11 +117,11 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
         FRI_HIP(ctx, hipEventCreateWithFlags(&V.ev_open, hipEventDisableTiming));
     }
     // members per launch pair: what the byte budget holds, or the hook's count
-    const size_t per_member = Sections(1, hw, Q, vw, pw).total;
+    const size_t per_member = Sections(1, hw, Q, vw, pw, pow).total;
     size_t chunk = V.chunk ? V.chunk : std::max<size_t>(VERIFY_CHUNK_BYTES / per_member, 1);
     chunk = std::min<size_t>(chunk, batch);
-    while (Sections(chunk, hw, Q, vw, pw).total > V.cap) {
-        const size_t need = Sections(chunk, hw, Q, vw, pw).total;
+    while (Sections(chunk, hw, Q, vw, pw, pow).total > V.cap) {
+        const size_t need = Sections(chunk, hw, Q, vw, pw, pow).total;
         FRI_HIP(ctx, hipStreamSynchronize(ctx->stream));
         dfree(ctx, V.dev);
         V.dev = nullptr;
@@ -129,6 +145,7 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
     t.log_t = sh.log_t;
     t.log_blowup = sh.log_blowup;
     t.range = sh.max_index + 1;
+    t.pow_bits = grinding_bits;
     for (uint32_t k = 0; k <= L; k++) {
         t.w_m[k] = to_mont(root_of_unity(L - k));
         t.off_m[k] = to_mont(pow_std(sh.offset, (uint64_t)1 << k));
@@ -146,7 +163,7 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
     hipStream_t s = ctx->stream;
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t m = std::min<size_t>(chunk, batch - b0);
-        const Sections S(m, hw, Q, vw, pw);
+        const Sections S(m, hw, Q, vw, pw, pow);
         uint8_t* d = V.dev;
         FRI_HIP(ctx, upload_rows(d + S.head, head + b0 * head_stride, hw * 4, head_stride * 4, m, s));
         FRI_HIP(ctx, upload_rows(d + S.chan, chan_in + b0, sizeof(fri_channel_state), sizeof(fri_channel_state), m, s));
@@ -157,6 +174,7 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
             FRI_HIP(ctx, upload_rows(d + S.vals, values + b0 * Q * values_stride, vw * 4, values_stride * 4, m * Q, s));
             FRI_HIP(ctx, upload_rows(d + S.paths, paths + b0 * Q * paths_stride, pw * 4, paths_stride, m * Q, s));
         }
+        if (pow) FRI_HIP(ctx, upload_rows(d + S.nonce, nonces + b0, 8, 8, m, s));
         FRI_HIP(ctx, hipMemsetAsync(d + S.verdict, 0, m * 4, s));
         t.head = reinterpret_cast<const uint32_t*>(d + S.head);
         t.chan = reinterpret_cast<const uint32_t*>(d + S.chan);
@@ -165,6 +183,7 @@ extern "C" int fri_verify_batch(fri_ctx* ctx, const fri_verify_shape* shape, uin
         t.indices = reinterpret_cast<const uint64_t*>(d + S.idx);
         t.values = reinterpret_cast<const uint32_t*>(d + S.vals);
         t.paths = reinterpret_cast<const uint32_t*>(d + S.paths);
+        t.nonces = pow ? reinterpret_cast<const uint64_t*>(d + S.nonce) : nullptr;
         t.verdict = reinterpret_cast<uint32_t*>(d + S.verdict);
         t.members = (uint32_t)m;
         if (serial) {

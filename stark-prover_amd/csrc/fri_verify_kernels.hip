@@ -32,12 +32,21 @@ __device__ __forceinline__ uint32_t fri_path_off(const VerifyTask& t, uint32_t k
 
 // One lane per member, workgroups of one wave.  The lane walks its transcript
 // in verify_transcript's order as a sequence of units, each a few sends:
-//   q = -1: [trace root, 3 alphas], per layer (root, beta), the final value;
+//   q = -1: [trace root, 3 alphas], per layer (root, beta), the final value,
+//           with pow_bits > 0 the grinding nonce: after its
+//           send the state's top pow_bits bits must be zero (VB_POW), and the
+//           replay goes on whether they are or not;
 //   q >= 0: the query index, trace_count (value, path), per layer
 //           (value, path, sibling value, sibling path), a one-element layer's
 //           value once more first (fri_commit.rs:147-149).
 // A draw compares what the channel gives with the claimed word and rehashes.
 // Lanes past their member's last layer sit the unit out.
+// Two instantiations, each with its ONE call site of chan_send: without
+// grinding bits the kernel is the one it was before the nonce existed (163
+// VGPRs, 93 SGPRs spilled); as a run-time case in one kernel the nonce cost
+// that path 3 VGPRs, 13 more spilled SGPRs and 0.7-0.9% of its time
+// (profiles/verify_batch_pow.txt).
+template <bool POW>
 __global__ __launch_bounds__(64) void k_verify_chain(VerifyTask t) {
     const uint32_t b = blockIdx.x * 64u + threadIdx.x;
     if (b >= t.members) return;
@@ -64,10 +73,11 @@ __global__ __launch_bounds__(64) void k_verify_chain(VerifyTask t) {
     for (int q = -1; q < (int)Q; q++) {
         const uint32_t* vals = t.values + ((size_t)b * Q + (q < 0 ? 0 : q)) * t.val_words;
         const uint32_t* pth = t.paths + ((size_t)b * Q + (q < 0 ? 0 : q)) * t.path_words;
-        // units: q < 0: [0, tcu) the trace root, [tcu, tcu + ML) the layers, then the final value
+        // units: q < 0: [0, tcu) the trace root, [tcu, tcu + ML) the layers, then the final value,
+        //               then the nonce (pow_bits > 0)
         //        q >= 0: 0 the index, [1, 1 + tc) the trace openings, then the layers
         const uint32_t tcu = tc ? 1u : 0u;
-        const uint32_t units = q < 0 ? tcu + ML + 1u : 1u + tc + ML;
+        const uint32_t units = q < 0 ? tcu + ML + 1u + (POW ? 1u : 0u) : 1u + tc + ML;
 #pragma unroll 1
         for (uint32_t u = 0; u < units; u++) {
             uint32_t nsub;
@@ -75,7 +85,7 @@ __global__ __launch_bounds__(64) void k_verify_chain(VerifyTask t) {
             else nsub = u == 0 ? 1u : (u < 1u + tc ? 2u : (L - (u - 1u - tc) == 0u ? 5u : 4u));
 #pragma unroll 1
             for (uint32_t s = 0; s < nsub; s++) {
-                uint32_t kind = MSG_PATH, nd = 0u, v = 0u, draw = DRAW_NONE;
+                uint32_t kind = MSG_PATH, nd = 0u, v = 0u, vhi = 0u, draw = DRAW_NONE;
                 uint64_t claim = 0;
                 const uint32_t* p = head;
                 bool act = true;
@@ -88,8 +98,11 @@ __global__ __launch_bounds__(64) void k_verify_chain(VerifyTask t) {
                         if (s == 0) { kind = MSG_ROOT; nd = 2u; p = head + hb + 8 * k; act = k < nl; }
                         // (k = ML - 1 reads the final value's word, inside the head, and sits out)
                         else { draw = DRAW_FIELD; claim = head[hb + 8 * ML + k]; act = k + 1 < nl; }
-                    } else {
+                    } else if (!POW || u == tcu + ML) {
                         kind = MSG_VALUE; v = head[hb + 9 * ML - 1];
+                    } else {                             // the nonce: every lane, a full 64-bit number
+                        const uint64_t n = t.nonces[b];
+                        kind = MSG_VALUE; v = (uint32_t)n; vhi = (uint32_t)(n >> 32);
                     }
                 } else if (u == 0) {
                     draw = DRAW_INDEX; claim = t.indices[(size_t)b * Q + q];
@@ -109,15 +122,18 @@ __global__ __launch_bounds__(64) void k_verify_chain(VerifyTask t) {
                     const uint64_t got = draw == DRAW_FIELD ? (uint64_t)chan_beta(cs) : chan_int(cs, t.range);
                     if (!has || got != claim) bad |= VB_CHANNEL;
                 }
-                chan_send(cs, has, kind, RecordNodes{p}, nd, v);
+                chan_send(cs, has, kind, RecordNodes{p}, nd, v, POW ? vhi : 0u);
             }
         }
+        // the nonce's send ends the q = -1 pass: the top pow_bits (1..32) bits of the state are those of cs[0]
+        if (POW && q < 0 && (cs[0] >> (32u - t.pow_bits))) bad |= VB_POW;
     }
     if (bad) atomicOr(&t.verdict[b], bad);
 }
 
 void launch_verify_chain(const VerifyTask& t, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify_chain, dim3((t.members + 63u) / 64u), dim3(64), 0, s, t);
+    if (t.pow_bits) hipLaunchKernelGGL(k_verify_chain<true>, dim3((t.members + 63u) / 64u), dim3(64), 0, s, t);
+    else hipLaunchKernelGGL(k_verify_chain<false>, dim3((t.members + 63u) / 64u), dim3(64), 0, s, t);
 }
 
 // --------------------------------------------------------------- openings ---

@@ -1171,6 +1171,8 @@ struct Packed {
     std::vector<uint8_t> paths;
     std::vector<uint32_t> reasons;             // a host decision (FRI_VERIFY_MALFORMED) or 0
     std::vector<uint8_t> host;                 // 1: left to the host verifier
+    uint32_t grinding_bits = 0;                // > 0: the message after the final value is the member's nonce
+    std::vector<uint64_t> nonces;              // per member (zeros without grinding bits)
 };
 enum class PackRc { Ok, Malformed, Host };
 
@@ -1185,13 +1187,14 @@ bool canonical_hex(const std::vector<uint8_t>& m) {
 // wrong length, a value, challenge or final value >= p, a one-element layer
 // whose doubled value differs).  Host: a root message that is not canonical
 // lowercase hex cannot be packed as raw bytes (and a final value >= p that no
-// query compares): the host verifier decides.
+// query compares): the host verifier decides.  With grinding bits one more
+// message, the nonce after the final value, which must be 8 bytes.
 PackRc pack_member(Packed& pk, size_t b, const Msgs& msgs, size_t nl, const std::string& state) {
     const uint32_t L = pk.sh.log_n, ML = pk.sh.max_layers, Q = pk.sh.num_queries, tc = pk.sh.trace_count;
     if (nl == 0 || nl > L + 1u) return PackRc::Malformed;
     size_t per_q = 1 + 2 * tc;
     for (size_t k = 0; k < nl; k++) per_q += (L - k == 0) ? 5 : 4;
-    if (msgs.size() != (tc ? 4 : 0) + 2 * nl + Q * per_q) return PackRc::Malformed;
+    if (msgs.size() != (tc ? 4 : 0) + 2 * nl + (pk.grinding_bits ? 1 : 0) + Q * per_q) return PackRc::Malformed;
     const size_t hb = tc ? 11 : 0;
     uint32_t* head = pk.head.data() + b * pk.hw;
     size_t pos = 0;
@@ -1220,6 +1223,11 @@ PackRc pack_member(Packed& pk, size_t b, const Msgs& msgs, size_t nl, const std:
     }
     if (Q == 0 && msgs[pos].size() == 8 && be_u64(msgs[pos]) >= P) to_host = true;
     value(head[hb + 9 * ML - 1]);
+    if (pk.grinding_bits) {
+        const auto& nm = msgs[pos++];
+        if (nm.size() != 8) malformed = true;
+        else pk.nonces[b] = be_u64(nm);
+    }
     for (size_t q = 0; q < Q; q++) {
         const auto& im = msgs[pos++];
         if (im.size() != 8) malformed = true;
@@ -1261,9 +1269,11 @@ PackRc pack_member(Packed& pk, size_t b, const Msgs& msgs, size_t nl, const std:
 
 Packed pack_batch(const std::vector<Msgs>& t, uint32_t log_n, const std::vector<size_t>& n_layers, size_t num_queries,
                   size_t max_index, uint32_t tc, uint32_t log_t, uint32_t log_blowup, FE offset,
-                  const std::vector<std::string>& states) {
+                  const std::vector<std::string>& states, uint32_t grinding_bits) {
     const size_t B = t.size();
     Packed pk;
+    pk.grinding_bits = grinding_bits;
+    pk.nonces.assign(B, 0);
     size_t ML = 1;
     for (size_t nl : n_layers)
         if (nl <= log_n + 1u) ML = std::max(ML, nl);
@@ -1297,6 +1307,7 @@ Packed pack_batch(const std::vector<Msgs>& t, uint32_t log_n, const std::vector<
         std::fill(pk.values.begin() + b * Q * pk.vw, pk.values.begin() + (b + 1) * Q * pk.vw, 0u);
         std::fill(pk.indices.begin() + b * Q, pk.indices.begin() + (b + 1) * Q, uint64_t{0});
         std::fill(pk.paths.begin() + b * Q * pk.pb, pk.paths.begin() + (b + 1) * Q * pk.pb, uint8_t{0});
+        pk.nonces[b] = 0;
         if (rc == PackRc::Malformed) pk.reasons[b] = FRI_VERIFY_MALFORMED;
         else pk.host[b] = 1;
     }
@@ -1322,12 +1333,22 @@ std::vector<bool> verify_packed(Packed& pk, const std::function<bool(size_t)>& h
         std::vector<uint32_t> got(B, 0);
         for (size_t b0 = 0; b0 < B; b0 += 65535) {
             const size_t m = std::min<size_t>(65535, B - b0);
-            gpu->check(fri_verify_batch(gpu->ctx(), &pk.sh, static_cast<uint32_t>(m), pk.chan.data() + b0,
-                                        pk.n_layers.data() + b0, pk.sh.trace_count ? pk.a_last.data() + b0 : nullptr,
-                                        pk.head.data() + b0 * pk.hw, pk.hw, pk.indices.data() + b0 * Q,
-                                        pk.values.data() + b0 * Q * pk.vw, pk.vw, pk.paths.data() + b0 * Q * pk.pb,
-                                        std::max<size_t>(pk.pb, 1), got.data() + b0),
-                       "fri_verify_batch");
+            const uint32_t* alast = pk.sh.trace_count ? pk.a_last.data() + b0 : nullptr;
+            const uint32_t mm = static_cast<uint32_t>(m);
+            const size_t ps = std::max<size_t>(pk.pb, 1);
+            if (pk.grinding_bits)
+                gpu->check(fri_verify_batch_pow(gpu->ctx(), &pk.sh, mm, pk.chan.data() + b0, pk.n_layers.data() + b0,
+                                                alast, pk.head.data() + b0 * pk.hw, pk.hw, pk.indices.data() + b0 * Q,
+                                                pk.values.data() + b0 * Q * pk.vw, pk.vw,
+                                                pk.paths.data() + b0 * Q * pk.pb, ps, pk.grinding_bits,
+                                                pk.nonces.data() + b0, got.data() + b0),
+                           "fri_verify_batch_pow");
+            else
+                gpu->check(fri_verify_batch(gpu->ctx(), &pk.sh, mm, pk.chan.data() + b0, pk.n_layers.data() + b0,
+                                            alast, pk.head.data() + b0 * pk.hw, pk.hw, pk.indices.data() + b0 * Q,
+                                            pk.values.data() + b0 * Q * pk.vw, pk.vw,
+                                            pk.paths.data() + b0 * Q * pk.pb, ps, got.data() + b0),
+                           "fri_verify_batch");
         }
         for (size_t b = 0; b < B; b++)
             if (!pk.reasons[b] && !pk.host[b]) mask[b] = got[b];
@@ -1344,16 +1365,18 @@ std::vector<bool> verify_packed(Packed& pk, const std::function<bool(size_t)>& h
 std::vector<bool> verify_fri_batch(const std::vector<Msgs>& transcripts, uint32_t log_n,
                                    const std::vector<size_t>& n_layers, size_t num_queries, size_t max_index, FE offset,
                                    const std::vector<std::string>& channel_states, std::shared_ptr<Gpu> gpu,
-                                   std::vector<uint32_t>* reasons) {
+                                   std::vector<uint32_t>* reasons, uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     const size_t B = transcripts.size();
     if (n_layers.size() != B || (!channel_states.empty() && channel_states.size() != B))
         throw Panic("verify_fri_batch: one n_layers and channel state per transcript");
     if (reasons) reasons->clear();
     if (B == 0) return {};
-    Packed pk = pack_batch(transcripts, log_n, n_layers, num_queries, max_index, 0, 0, 0, offset, channel_states);
+    Packed pk = pack_batch(transcripts, log_n, n_layers, num_queries, max_index, 0, 0, 0, offset, channel_states,
+                           grinding_bits);
     auto host = [&](size_t b) {
         return verify_fri(transcripts[b], log_n, n_layers[b], num_queries, max_index, offset,
-                          channel_states.empty() ? std::string() : channel_states[b]);
+                          channel_states.empty() ? std::string() : channel_states[b], grinding_bits);
     };
     return verify_packed(pk, host, std::move(gpu), reasons, "verify_fri_batch");
 }
@@ -1362,7 +1385,8 @@ std::vector<bool> verify_fibsq_batch(const std::vector<Msgs>& transcripts, const
                                      uint32_t log_t, uint32_t log_blowup, size_t num_queries,
                                      const std::vector<size_t>& n_layers, FE offset,
                                      const std::vector<std::string>& channel_states, std::shared_ptr<Gpu> gpu,
-                                     std::vector<uint32_t>* reasons) {
+                                     std::vector<uint32_t>* reasons, uint32_t grinding_bits) {
+    check_grinding_bits(grinding_bits);
     const size_t B = transcripts.size();
     if (a_last.size() != B || n_layers.size() != B || (!channel_states.empty() && channel_states.size() != B))
         throw Panic("verify_fibsq_batch: one a_last, n_layers and channel state per transcript");
@@ -1370,11 +1394,12 @@ std::vector<bool> verify_fibsq_batch(const std::vector<Msgs>& transcripts, const
     if (B == 0) return {};
     const uint32_t L = log_t + log_blowup;
     const size_t max_index = (size_t{1} << L) - 2 * (size_t{1} << log_blowup) - 1;
-    Packed pk = pack_batch(transcripts, L, n_layers, num_queries, max_index, 3, log_t, log_blowup, offset, channel_states);
+    Packed pk = pack_batch(transcripts, L, n_layers, num_queries, max_index, 3, log_t, log_blowup, offset, channel_states,
+                           grinding_bits);
     for (size_t b = 0; b < B; b++) pk.a_last[b] = static_cast<uint32_t>(a_last[b].value());
     auto host = [&](size_t b) {
         return verify_fibsq(transcripts[b], a_last[b], log_t, log_blowup, num_queries, n_layers[b], offset,
-                            channel_states.empty() ? std::string() : channel_states[b]);
+                            channel_states.empty() ? std::string() : channel_states[b], grinding_bits);
     };
     return verify_packed(pk, host, std::move(gpu), reasons, "verify_fibsq_batch");
 }

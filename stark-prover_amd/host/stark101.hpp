@@ -696,15 +696,21 @@ bool verify_fibsq(const std::vector<std::vector<uint8_t>>& messages, FE a_last, 
 // are not canonical lowercase hex goes to the host verifier.  Mismatched
 // lengths panic; an empty batch returns an empty vector.  Without a Gpu: the
 // thread's default, or the one-device Gpu beside a default team.
+// grinding_bits > 0 (one value for the batch; above 32 panics): every
+// transcript carries its 8-byte nonce after the final value (any other length
+// is FRI_VERIFY_MALFORMED), the device call is fri_verify_batch_pow and a state
+// that lacks the bits after the nonce's send is FRI_VERIFY_POW.
 std::vector<bool> verify_fri_batch(const std::vector<std::vector<std::vector<uint8_t>>>& transcripts, uint32_t log_n,
                                    const std::vector<size_t>& n_layers, size_t num_queries, size_t max_index,
                                    FE offset = FE(FRI_GENERATOR), const std::vector<std::string>& channel_states = {},
-                                   std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr);
+                                   std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr,
+                                   uint32_t grinding_bits = 0);
 std::vector<bool> verify_fibsq_batch(const std::vector<std::vector<std::vector<uint8_t>>>& transcripts,
                                      const std::vector<FE>& a_last, uint32_t log_t, uint32_t log_blowup,
                                      size_t num_queries, const std::vector<size_t>& n_layers,
                                      FE offset = FE(FRI_GENERATOR), const std::vector<std::string>& channel_states = {},
-                                     std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr);
+                                     std::shared_ptr<Gpu> gpu = nullptr, std::vector<uint32_t>* reasons = nullptr,
+                                   uint32_t grinding_bits = 0);
 
 // ---------------------------------------------------- polynomial layer (GPU)
 // evaluate() at every coset point (fri_commit.rs:78): the LDE.

@@ -69,6 +69,7 @@ GRIND_DEVICE_MIN_BITS = 8
 # FRI_VERIFY_*: the verdict bits of fri_verify_batch (0 = accepted)
 VERIFY_CHANNEL, VERIFY_TRACE_PATH, VERIFY_COMPOSITION, VERIFY_FRI_PATH = 1, 2, 4, 8
 VERIFY_FOLD, VERIFY_FINAL, VERIFY_MALFORMED = 16, 32, 64
+VERIFY_POW = 128            # the state after the nonce's send lacks the grinding bits (fri_verify_batch_pow)
 
 
 class FriError(RuntimeError):
@@ -233,6 +234,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "fri_verify_batch": (i32, [vp, ctypes.POINTER(VerifyShape), u32, ctypes.POINTER(ChannelState), pu32, pu32,
                                    pu32, sz, ctypes.POINTER(ctypes.c_uint64), pu32, sz,
                                    ctypes.POINTER(ctypes.c_uint8), sz, pu32]),
+        "fri_verify_batch_pow": (i32, [vp, ctypes.POINTER(VerifyShape), u32, ctypes.POINTER(ChannelState), pu32, pu32,
+                                       pu32, sz, ctypes.POINTER(ctypes.c_uint64), pu32, sz,
+                                       ctypes.POINTER(ctypes.c_uint8), sz, u32, ctypes.POINTER(ctypes.c_uint64),
+                                       pu32]),
         "fri_debug_set_verify_chunk": (i32, [vp, u32]),
     }
     for name, (res, args) in sig.items():
@@ -858,20 +863,33 @@ class Context:
         self._check(self.lib.fri_debug_set_grind_window(self.h, log_window))
 
     def verify_batch(self, shape: "VerifyShape", batch: int, chan, n_layers, a_last, head, head_stride: int,
-                     indices, values, values_stride: int, paths, paths_stride: int, verdict=None) -> np.ndarray:
+                     indices, values, values_stride: int, paths, paths_stride: int, verdict=None,
+                     grinding_bits: int = 0, nonces=None) -> np.ndarray:
         """fri_verify_batch over the raw ABI: ``shape`` a VerifyShape, ``chan``
         a (batch, 36) uint8 array of fri_channel_state records, the other
         arrays as fri_amd.h lays them out (``PackedTranscripts.abi_args()``
         gives them all).  Returns the verdict masks, a uint32 array (the
-        caller's ``verdict`` when given): 0 = accepted, else VERIFY_* bits."""
+        caller's ``verdict`` when given): 0 = accepted, else VERIFY_* bits.
+        ``grinding_bits`` > 0: fri_verify_batch_pow with ``nonces``, a
+        (batch,) uint64 array of the members' grinding nonces."""
         if verdict is None:
             verdict = np.zeros(max(batch, 1), dtype=np.uint32)
         u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
-        rc = self.lib.fri_verify_batch(self.h, ctypes.byref(shape), batch,
-                                       chan.ctypes.data_as(ctypes.POINTER(ChannelState)), _ptr(n_layers),
-                                       _ptr(a_last) if a_last is not None else None, _ptr(head), head_stride,
-                                       indices.ctypes.data_as(u64p), _ptr(values), values_stride,
-                                       paths.ctypes.data_as(u8p), paths_stride, _ptr(verdict))
+        args = (self.h, ctypes.byref(shape), batch,
+                chan.ctypes.data_as(ctypes.POINTER(ChannelState)), _ptr(n_layers),
+                _ptr(a_last) if a_last is not None else None, _ptr(head), head_stride,
+                indices.ctypes.data_as(u64p), _ptr(values), values_stride,
+                paths.ctypes.data_as(u8p), paths_stride)
+        if grinding_bits:
+            if grinding_bits < 0:
+                raise FriError(FRI_EINVAL, "grinding_bits must be 0..32")
+            if nonces is not None:
+                nonces = np.ascontiguousarray(nonces, dtype=np.uint64)
+            rc = self.lib.fri_verify_batch_pow(*args, grinding_bits,
+                                               nonces.ctypes.data_as(u64p) if nonces is not None else None,
+                                               _ptr(verdict))
+        else:
+            rc = self.lib.fri_verify_batch(*args, _ptr(verdict))
         self._check(rc)
         return verdict[:batch]
 
@@ -2119,7 +2137,8 @@ class PackedTranscripts:
     decision (VERIFY_MALFORMED) or 0; ``host[b]`` marks a member the existing
     host verifier decides (its root messages are not canonical lowercase hex,
     so they cannot be packed as raw bytes).  Both kinds hold zeros in the
-    arrays and n_layers 1."""
+    arrays and n_layers 1.  ``grinding_bits`` > 0: every member's message
+    after the final value is its grinding nonce, in ``nonces``."""
     shape: VerifyShape
     chan: np.ndarray          # (batch, 36) uint8: fri_channel_state
     n_layers: np.ndarray      # (batch,) uint32
@@ -2130,6 +2149,8 @@ class PackedTranscripts:
     paths: np.ndarray         # (batch, num_queries, paths_stride) uint8
     reasons: np.ndarray       # (batch,) uint32
     host: np.ndarray          # (batch,) bool
+    nonces: Optional[np.ndarray] = None    # (batch,) uint64 (zeros without grinding bits)
+    grinding_bits: int = 0
 
     @property
     def batch(self) -> int:
@@ -2151,7 +2172,7 @@ def verify_record_strides(log_n: int, max_layers: int, trace_count: int) -> tupl
 def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layers: Sequence[int], num_queries: int,
                      max_index: int, trace_count: int = 0, log_t: int = 0, log_blowup: int = 0,
                      a_last: Optional[Sequence[int]] = None, offset: int = GENERATOR,
-                     channel_states: Optional[Sequence[str]] = None) -> PackedTranscripts:
+                     channel_states: Optional[Sequence[str]] = None, grinding_bits: int = 0) -> PackedTranscripts:
     """Pure host code: the messages of verify_fri (trace_count 0) or
     verify_fibsq (trace_count 3) transcripts into fri_verify_batch's arrays.
     A member is decided here only where the host verifier certainly rejects
@@ -2160,7 +2181,10 @@ def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
     >= p, a one-element layer whose doubled value differs.  A member whose
     root messages are not canonical lowercase hex is left to the host verifier
     (``host``), as is the one case _verify_transcript does not settle by
-    length, an FRI value that is not 8 bytes."""
+    length, an FRI value that is not 8 bytes.  ``grinding_bits`` > 0: one
+    more message per member, the nonce after the final value, which must be 8
+    bytes (else VERIFY_MALFORMED) and goes into ``nonces``."""
+    _check_grinding_bits(grinding_bits)
     B = len(transcripts)
     if len(n_layers) != B or (channel_states is not None and len(channel_states) != B) or \
             (trace_count and (a_last is None or len(a_last) != B)):
@@ -2176,7 +2200,8 @@ def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
     pk = PackedTranscripts(shape, np.zeros((B, 36), np.uint8), np.ones(B, np.uint32),
                            np.zeros(B, np.uint32) if tc else None, np.zeros((B, hw), np.uint32),
                            np.zeros((B, Q), np.uint64), np.zeros((B, Q, vw), np.uint32),
-                           np.zeros((B, Q, max(pb, 1)), np.uint8), np.zeros(B, np.uint32), np.zeros(B, bool))
+                           np.zeros((B, Q, max(pb, 1)), np.uint8), np.zeros(B, np.uint32), np.zeros(B, bool),
+                           np.zeros(B, np.uint64), grinding_bits)
 
     class _Malformed(Exception):
         pass
@@ -2205,7 +2230,7 @@ def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
             if not 1 <= nl <= L + 1:
                 raise _Malformed()
             per_q = 1 + 2 * tc + sum(5 if L - k == 0 else 4 for k in range(nl))
-            if len(msgs) != (4 if tc else 0) + 2 * nl + Q * per_q:
+            if len(msgs) != (4 if tc else 0) + 2 * nl + (1 if grinding_bits else 0) + Q * per_q:
                 raise _Malformed()
             head, idxs, vals, pths = np.zeros(hw, np.uint32), [], np.zeros((Q, vw), np.uint32), []
             it = iter(msgs)
@@ -2221,6 +2246,12 @@ def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
             if Q == 0 and len(fin) == 8 and int.from_bytes(fin, "big") >= P:
                 raise _Host()                 # no query ever compares it
             head[hb + 9 * ML - 1] = u64(fin)
+            nonce = 0
+            if grinding_bits:
+                m = next(it)
+                if len(m) != 8:
+                    raise _Malformed()
+                nonce = int.from_bytes(m, "big")
             for q in range(Q):
                 m = next(it)
                 if len(m) != 8:
@@ -2258,6 +2289,7 @@ def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
         if tc:
             pk.a_last[b] = int(a_last[b]) % P     # verify_fibsq reduces it too (fibsq_cp_at)
         pk.head[b] = head
+        pk.nonces[b] = nonce
         pk.values[b] = vals
         for q in range(Q):
             pk.indices[b, q] = idxs[q]
@@ -2287,6 +2319,8 @@ def unpack_transcripts(pk: PackedTranscripts) -> List[Optional[List[bytes]]]:
             if k < nl - 1:
                 msgs.append(be(head[hb + 8 * ML + k]))
         msgs.append(be(head[hb + 9 * ML - 1]))
+        if pk.grinding_bits:
+            msgs.append(be(pk.nonces[b]))
         for q in range(Q):
             vals, raw = pk.values[b, q], pk.paths[b, q].tobytes()
             msgs.append(be(pk.indices[b, q]))
@@ -2317,7 +2351,8 @@ def _verify_packed(pk: PackedTranscripts, host_verify, ctx: Optional[Context], r
             b1 = min(pk.batch, b0 + BATCH_MAX)
             got = ctx.verify_batch(args[0], b1 - b0, pk.chan[b0:b1], pk.n_layers[b0:b1],
                                    pk.a_last[b0:b1] if pk.a_last is not None else None, pk.head[b0:b1], args[6],
-                                   pk.indices[b0:b1], pk.values[b0:b1], args[9], pk.paths[b0:b1], args[11])
+                                   pk.indices[b0:b1], pk.values[b0:b1], args[9], pk.paths[b0:b1], args[11],
+                                   grinding_bits=pk.grinding_bits, nonces=pk.nonces[b0:b1])
             mask[b0:b1] = np.where(device[b0:b1], got, mask[b0:b1])
     for b in np.flatnonzero(pk.host):
         mask[b] = 0 if host_verify(int(b)) else VERIFY_MALFORMED
@@ -2328,11 +2363,15 @@ def _verify_packed(pk: PackedTranscripts, host_verify, ctx: Optional[Context], r
 
 def verify_fri_batch(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layers: Sequence[int], num_queries: int,
                      max_index: int, offset: int = GENERATOR, channel_states: Optional[Sequence[str]] = None,
-                     ctx: Optional[Context] = None, reasons: Optional[list] = None) -> List[bool]:
+                     ctx: Optional[Context] = None, reasons: Optional[list] = None,
+                     grinding_bits: int = 0) -> List[bool]:
     """verify_fri for many transcripts of one shape (log_n, num_queries,
     max_index, offset), member b with its own n_layers[b] and channel state,
     in one device call (fri_verify_batch).  Returns what a loop of verify_fri
-    returns; ``reasons`` (a list) receives the VERIFY_* masks."""
+    returns; ``reasons`` (a list) receives the VERIFY_* masks.
+    ``grinding_bits`` > 0 (one value for the batch): every transcript carries
+    its nonce after the final value (fri_verify_batch_pow, VERIFY_POW)."""
+    _check_grinding_bits(grinding_bits)
     if len(n_layers) != len(transcripts) or (channel_states is not None and len(channel_states) != len(transcripts)):
         raise FriError(FRI_EINVAL, "one n_layers and channel state per transcript")
     if len(transcripts) == 0:
@@ -2340,19 +2379,21 @@ def verify_fri_batch(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layer
             reasons[:] = []
         return []
     pk = pack_transcripts(transcripts, log_n, n_layers, num_queries, max_index, offset=offset,
-                          channel_states=channel_states)
+                          channel_states=channel_states, grinding_bits=grinding_bits)
     state = lambda b: channel_states[b] if channel_states is not None else ""
     return _verify_packed(pk, lambda b: verify_fri(transcripts[b], log_n, n_layers[b], num_queries, max_index, offset,
-                                                   state(b)), ctx, reasons)
+                                                   state(b), grinding_bits), ctx, reasons)
 
 
 def verify_fibsq_batch(transcripts: Sequence[Sequence[bytes]], a_last: Sequence[int], log_t: int, log_blowup: int,
                        num_queries: int, n_layers: Sequence[int], offset: int = GENERATOR,
                        channel_states: Optional[Sequence[str]] = None, ctx: Optional[Context] = None,
-                       reasons: Optional[list] = None) -> List[bool]:
+                       reasons: Optional[list] = None, grinding_bits: int = 0) -> List[bool]:
     """verify_fibsq for many transcripts of one shape, member b with its own
     a_last[b], n_layers[b] and channel state, in one device call.  Returns what
-    a loop of verify_fibsq returns; ``reasons`` receives the VERIFY_* masks."""
+    a loop of verify_fibsq returns; ``reasons`` receives the VERIFY_* masks.
+    ``grinding_bits`` > 0: as verify_fri_batch's."""
+    _check_grinding_bits(grinding_bits)
     B = len(transcripts)
     if len(a_last) != B or len(n_layers) != B or (channel_states is not None and len(channel_states) != B):
         raise FriError(FRI_EINVAL, "one a_last, n_layers and channel state per transcript")
@@ -2363,10 +2404,10 @@ def verify_fibsq_batch(transcripts: Sequence[Sequence[bytes]], a_last: Sequence[
     L = log_t + log_blowup
     a_last = [int(a) % P for a in a_last]     # verify_fibsq reduces it (FE / fibsq_cp_at)
     pk = pack_transcripts(transcripts, L, n_layers, num_queries, (1 << L) - 2 * (1 << log_blowup) - 1, 3, log_t,
-                          log_blowup, a_last, offset, channel_states)
+                          log_blowup, a_last, offset, channel_states, grinding_bits)
     state = lambda b: channel_states[b] if channel_states is not None else ""
     return _verify_packed(pk, lambda b: verify_fibsq(transcripts[b], a_last[b], log_t, log_blowup, num_queries,
-                                                     n_layers[b], offset, state(b)), ctx, reasons)
+                                                     n_layers[b], offset, state(b), grinding_bits), ctx, reasons)
 
 
 def fri_commit_sharded(coeffs: Sequence[int], log_n: int, channel: Channel, ctx: Context,

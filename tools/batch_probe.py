@@ -42,7 +42,9 @@ the median of --reps runs, in microseconds per proof:
 against a loop of the C++ verify_fibsq on one core and over 16 threads
 (build/verify_native, over min(B, 256) members).
 
-    python tools/batch_probe.py --verify [--reps 5] [--out profiles/verify_batch.txt]
+    python tools/batch_probe.py --verify [--reps 5] [--out profiles/verify_batch.txt] [--grinding-bits N]
+--grinding-bits N proves with N bits of proof of work and verifies with N bits
+(fri_verify_batch_pow, and the host verifiers at the same bits).
 """
 import argparse
 import ctypes
@@ -209,11 +211,11 @@ VERIFY_THREADS = 16
 
 def verify_mode(args, reps, say):
     lib = fri_amd.load_library()
-    lb = PROVE_LOG_BLOWUP
+    lb, bits = PROVE_LOG_BLOWUP, args.grinding_bits
     native = os.path.join(ROOT, "stark-prover_amd", "build", "verify_native")
     ctx = fri_amd.Context(0, max(t for t, _ in VERIFY_SHAPES) + lb)
     say(f"batch_probe --verify: {lib.fri_version().decode()}, blowup {1 << lb}, us per proof, median of {reps} "
-        "(warm; transcripts from prove_fibsq_batch)")
+        f"(warm; transcripts from prove_fibsq_batch; {bits} grinding bits)")
     say("(a) fri_verify_batch with its copies, two streams / FRI_VERIFY_SERIAL=1   (b) kernel classes alone   "
         "(c) packing in the C++ mirror")
     say(f"loop 1 / loop {VERIFY_THREADS}: a loop of the C++ verify_fibsq on one core / over {VERIFY_THREADS} threads;  "
@@ -226,17 +228,19 @@ def verify_mode(args, reps, say):
         m = 256
         a1s = [1000003 * b + 3141592 for b in range(m)]
         chans = [fri_amd.Channel() for _ in a1s]
-        sps = fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx)
+        sps = fri_amd.prove_fibsq_batch(a1s, log_t, lb, Q, chans, ctx=ctx, grinding_bits=bits)
         pk = fri_amd.pack_transcripts([ch.proof for ch in chans], L, [sp.fri.n_layers for sp in sps], Q,
-                                      (1 << L) - 2 * (1 << lb) - 1, 3, log_t, lb, [sp.a_last for sp in sps])
+                                      (1 << L) - 2 * (1 << lb) - 1, 3, log_t, lb, [sp.a_last for sp in sps],
+                                      grinding_bits=bits)
         assert not pk.reasons.any() and not pk.host.any()
         for B in VERIFY_BATCHES:
             rep = -(-B // m)
             cut = lambda a: np.ascontiguousarray(np.concatenate([a] * rep)[:B])   # noqa: E731
             pb = fri_amd.PackedTranscripts(pk.shape, cut(pk.chan), cut(pk.n_layers), cut(pk.a_last), cut(pk.head),
-                                           cut(pk.indices), cut(pk.values), cut(pk.paths), cut(pk.reasons), cut(pk.host))
+                                           cut(pk.indices), cut(pk.values), cut(pk.paths), cut(pk.reasons), cut(pk.host),
+                                           cut(pk.nonces), bits)
             a = pb.abi_args()
-            call = lambda: ctx.verify_batch(*a)   # noqa: E731
+            call = lambda: ctx.verify_batch(*a, grinding_bits=bits, nonces=pb.nonces)   # noqa: E731
             assert not call().any(), "the device rejected an honest transcript"
             ts = sorted(med_us(call, 1, B) for _ in range(reps))
             dev, lo, hi = ts[reps // 2], ts[0], ts[-1]
@@ -250,7 +254,8 @@ def verify_mode(args, reps, say):
                 call()
             chain, opn = (ctx.profile(c)[0] * 1e3 / reps / B for c in ("verify_chain", "verify_open"))
             ctx.set_profiling(False)
-            out = subprocess.run([native, str(log_t), str(lb), str(Q), str(B), str(reps), str(VERIFY_THREADS)],
+            out = subprocess.run([native, str(log_t), str(lb), str(Q), str(B), str(reps), str(VERIFY_THREADS),
+                                  str(bits)],
                                  capture_output=True, text=True, timeout=1500)
             nat = json.loads(out.stdout.strip().splitlines()[-1])
             assert nat.get("accepted"), out.stdout + out.stderr
@@ -280,6 +285,7 @@ def main():
     ap.add_argument("--prove", action="store_true", help="the batched prover against a loop of prove_fibsq")
     ap.add_argument("--batches", type=int, nargs="*", default=None, help="--prove: the batch sizes (default: all)")
     ap.add_argument("--verify", action="store_true", help="the batched verifier against loops of verify_fibsq")
+    ap.add_argument("--grinding-bits", type=int, default=0, help="--verify: prove and verify with this many bits")
     args = ap.parse_args()
     reps = max(args.reps, 5)
     if args.verify:
