@@ -562,7 +562,8 @@ int fri_batch_decommit_query(fri_ctx* ctx, uint32_t member, uint64_t index, uint
  * is served, and the call returns the first failing member's code.
  *
  * fri_batch_query_round: one query of every member of the resident batch in
- * ONE launch and ONE read-back.  indices[b]: member b's query index (taken
+ * ONE launch and ONE read-back (per chunk of fri_batch_query_phase's staging
+ * budget: one chunk below 256 MiB of records).  indices[b]: member b's query index (taken
  * mod each layer's size, as fri_decommit_query; < 2^L when trace_count > 0).
  * skip (may be NULL): skip[b] != 0 leaves member b out; so is a member whose
  * commit failed.  trace_count = 0: the FRI openings only (serves a plain
@@ -627,7 +628,9 @@ int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* 
  * then gathers the records of the drawn indices, and one read-back brings
  * indices, records and final states to the host.  The members go through
  * device and pinned staging in chunks of a 256 MiB budget
- * (fri_debug_set_query_chunk: members per chunk, 0 = by the budget).  The call
+ * (fri_debug_set_query_chunk: members per chunk, 0 = by the budget; the hook
+ * governs fri_batch_query_round too, which stages through the same chunks, a
+ * batch under the budget in one launch and one read-back).  The call
  * reads and changes nothing of the resident batch: the commit generation does
  * not move and fri_batch_query_round serves the same batch afterwards.
  * FRI_ENOMEM leaves the context usable and what was resident readable.

@@ -76,7 +76,7 @@ struct TreeNodes {
     uint32_t L;
     uint64_t leaf;
     __device__ __forceinline__ void node(uint32_t i, uint32_t out[8]) const {
-        const uint32_t* d = tree + 8 * (level_offset(L, i) + ((leaf >> i) ^ 1u));
+        const uint32_t* d = sibling_digest(tree, L, i, leaf);
         const uint4 lo = reinterpret_cast<const uint4*>(d)[0], hi = reinterpret_cast<const uint4*>(d)[1];
         out[0] = lo.x; out[1] = lo.y; out[2] = lo.z; out[3] = lo.w;
         out[4] = hi.x; out[5] = hi.y; out[6] = hi.z; out[7] = hi.w;

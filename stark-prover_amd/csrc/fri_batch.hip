@@ -414,102 +414,13 @@ extern "C" int fri_fibsq_composition_commit_batch(fri_ctx* ctx, uint32_t log_t, 
     return run_batch(ctx, nullptr, coef, n, batch, L, offset, chan_in, flags, nullptr, out, status, true, (uint32_t)T);
 }
 
-extern "C" int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* skip, uint32_t trace_count,
-                                     uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
-                                     size_t paths_stride, size_t* paths_len) {
-    if (!ctx || !indices || !values || !paths || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
-    Batch& B = ctx->batch;
-    if (!B.resident)
-        return fail(ctx, FRI_ESTATE,
-                    "no resident batch: fri_batch_* serve the last fri_commit_batch until the next commit");
-    if (trace_count > 8) return fail(ctx, FRI_EINVAL, "trace_count must be 0..8");
-    const uint32_t L = B.log_n, batch = B.count;
-    if (trace_count && (!B.trace_resident || B.trace_count != batch || B.trace_log_t + B.trace_log_b != L))
-        return fail(ctx, FRI_ESTATE, "no resident trace batch behind this batch (fri_trace_commit_batch)");
-    // who is served, and the record's shape
-    uint32_t max_layers = 0, served = 0;
-    for (uint32_t b = 0; b < batch; b++) {
-        const uint32_t nl = (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers;
-        if (!nl) continue;
-        // (the FRI openings take any index, mod the layer's size, as fri_decommit_query; the trace's do not)
-        if (trace_count && (indices[b] >> L))
-            return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": index out of range");
-        max_layers = std::max(max_layers, nl);
-        served++;
-    }
-    auto fri_path_words = [&](uint32_t nl) { return 16 * ((size_t)nl * L - (size_t)nl * (nl ? nl - 1 : 0) / 2); };
-    const size_t tpath_words = (size_t)trace_count * 8 * L;
-    const size_t val_words = trace_count + 2 * (size_t)max_layers;
-    const size_t rec_words = val_words + tpath_words + fri_path_words(max_layers);
-    if (served && (values_stride < val_words || paths_stride < (tpath_words + fri_path_words(max_layers)) * 4)) {
-        paths_len[0] = (tpath_words + fri_path_words(max_layers)) * 4;
-        return fail(ctx, FRI_EINVAL,
-                    "record strides too small (values: trace_count + 2 per layer words; paths: see paths_len[0])");
-    }
-    for (uint32_t b = 0; b < batch; b++) paths_len[b] = 0;
-    if (!served) return FRI_OK;
-    FRI_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t meta_bytes = (size_t)batch * sizeof(BatchQueryMember), out_bytes = (size_t)batch * rec_words * 4;
-    size_t want[BB_N] = {};
-    want[BB_QMETA] = meta_bytes;
-    want[BB_QOUT] = out_bytes;
-    int rc;
-    if ((rc = hq_grow(ctx, meta_bytes + out_bytes))) return rc;
-    if ((rc = bufs_grow(ctx, B.b, want, 0))) return rc;
-    BatchQueryMember* hm = reinterpret_cast<BatchQueryMember*>(B.h_q);
-    const uint32_t* hout = reinterpret_cast<const uint32_t*>(B.h_q + meta_bytes);
-    for (uint32_t b = 0; b < batch; b++) {
-        hm[b].index = indices[b];
-        hm[b].n_layers = (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers;
-        hm[b].pad = 0;
-    }
-    BatchQuery bq{};
-    bq.layers = B.b.words(BB_LAYERS);
-    bq.trees = B.b.words(BB_TREES);
-    bq.lay_stride = B.lay_stride;
-    bq.tre_stride = B.tre_stride;
-    bq.tlde = B.b.words(BB_TLDE);
-    bq.ttree = B.b.words(BB_TTREE);
-    bq.tlde_stride = B.tlde_stride;
-    bq.ttree_stride = B.ttree_stride;
-    bq.mem = static_cast<const BatchQueryMember*>(B.b.dev[BB_QMETA]);
-    bq.out = B.b.words(BB_QOUT);
-    bq.rec_words = rec_words;
-    bq.trace_stride = trace_stride;
-    bq.log_n = L;
-    bq.trace_count = trace_count;
-    bq.max_layers = max_layers;
-    for (int k = 0; k <= B.lay.rmax + 1; k++) {
-        bq.layer_off[k] = (uint32_t)B.lay.layer_off[k];
-        bq.tree_off[k] = (uint32_t)B.lay.tree_off[k];
-    }
-    hipStream_t s = ctx->stream;
-    FRI_HIP(ctx, hipMemcpyAsync(B.b.dev[BB_QMETA], hm, meta_bytes, hipMemcpyHostToDevice, s));
-    launch_batch_query(bq, batch, s);
-    FRI_HIP(ctx, hipGetLastError());
-    FRI_HIP(ctx, hipMemcpyAsync(B.h_q + meta_bytes, bq.out, out_bytes, hipMemcpyDeviceToHost, s));
-    FRI_HIP(ctx, hipStreamSynchronize(s));
-    for (uint32_t b = 0; b < batch; b++) {
-        const uint32_t nl = hm[b].n_layers;
-        if (!nl) continue;
-        const uint32_t* rec = hout + b * rec_words;
-        uint32_t* v = values + b * values_stride;
-        uint8_t* p = paths + b * paths_stride;
-        memcpy(v, rec, trace_count * 4);
-        memcpy(v + trace_count, rec + trace_count, 2 * (size_t)nl * 4);
-        memcpy(p, rec + val_words, tpath_words * 4);
-        memcpy(p + tpath_words * 4, rec + val_words + tpath_words, fri_path_words(nl) * 4);
-        paths_len[b] = (tpath_words + fri_path_words(nl)) * 4;
-    }
-    ctx->err.clear();
-    return FRI_OK;
-}
-
-// ------------------------------------------------ the query phase (device) ----
-// fri_batch_query_phase: all the queries of every member, the channels' draws
-// and sends included, in chunks of members under a staging budget; per chunk
-// one upload, k_query_chain, k_batch_query_all and one read-back on the
-// context stream.  Reads and changes nothing of the resident batch.
+// ------------------------------------------------ the queries of a batch ----
+// fri_batch_query_round (one query of every member at the caller's indices)
+// and fri_batch_query_phase (all the queries of every member, the channels'
+// draws and sends included) are one run (run_queries) in chunks of members
+// under a staging budget; per chunk one upload, the phase's k_query_chain,
+// k_batch_query_all and one read-back on the context stream.  Reads and
+// changes nothing of the resident batch.
 namespace {
 constexpr size_t QUERY_CHUNK_BYTES = (size_t)256 << 20;   // device and pinned staging of one chunk
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -535,53 +446,50 @@ extern "C" int fri_debug_set_query_chunk(fri_ctx* ctx, uint32_t members) {
     return FRI_OK;
 }
 
-extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_t max_index, fri_channel_state* chan,
-                                     const uint8_t* skip, uint32_t trace_count, uint64_t trace_stride,
-                                     uint64_t* indices, uint32_t* values, size_t values_stride, uint8_t* paths,
-                                     size_t paths_stride, size_t* paths_len) {
-    static_assert(sizeof(fri_channel_state) == 36, "k_query_chain reads a channel state as 9 words");
-    if (!ctx || !chan || !paths_len || (num_queries && (!indices || !values || !paths)))
-        return fail(ctx, FRI_EINVAL, "null argument");
-    int rc = batch_ctx_ok(ctx);
-    if (rc) return rc;
-    Batch& B = ctx->batch;
+// The resident batch the queries are served from, and the trace batch behind it.
+static int query_batch_ok(fri_ctx* ctx, uint32_t trace_count) {
+    const Batch& B = ctx->batch;
     if (!B.resident)
         return fail(ctx, FRI_ESTATE,
                     "no resident batch: fri_batch_* serve the last fri_commit_batch until the next commit");
     if (trace_count > 8) return fail(ctx, FRI_EINVAL, "trace_count must be 0..8");
-    const uint32_t L = B.log_n, batch = B.count, Q = num_queries;
-    if (trace_count && (!B.trace_resident || B.trace_count != batch || B.trace_log_t + B.trace_log_b != L))
+    if (trace_count && (!B.trace_resident || B.trace_count != B.count || B.trace_log_t + B.trace_log_b != B.log_n))
         return fail(ctx, FRI_ESTATE, "no resident trace batch behind this batch (fri_trace_commit_batch)");
-    if (max_index >> 32) return fail(ctx, FRI_EINVAL, "max_index must be below 2^32");
-    // (the FRI openings take any index, mod the layer's size; the trace's do not)
-    if (trace_count && (max_index >> L)) return fail(ctx, FRI_EINVAL, "max_index must be below 2^log_n with trace_count > 0");
-    if (Q > FRI_VERIFY_MAX_QUERIES) return fail(ctx, FRI_EINVAL, "num_queries above FRI_VERIFY_MAX_QUERIES");
-    if (Q == 0) {
-        ctx->err.clear();
-        return FRI_OK;
-    }
+    return FRI_OK;
+}
+
+// The layers member b is served with: none when it is skipped or its commit failed.
+static uint32_t served_layers(const Batch& B, const uint8_t* skip, uint32_t b) {
+    return (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers;
+}
+
+// Q queries of every served member into the caller's records, which it scatters
+// from the chunks' staging.  The round: Q = 1 at idx_in[b], the gather alone.
+// The phase (chan != nullptr): the indices are drawn below `range` from chan[b],
+// which takes the openings and is written back with the indices (idx_out).
+// The arguments are the entry points', checked by them but for the strides.
+static int run_queries(fri_ctx* ctx, uint32_t Q, const uint64_t* idx_in, fri_channel_state* chan, uint64_t range,
+                       const uint8_t* skip, uint32_t trace_count, uint64_t trace_stride, uint64_t* idx_out,
+                       uint32_t* values, size_t values_stride, uint8_t* paths, size_t paths_stride, size_t* paths_len) {
+    Batch& B = ctx->batch;
+    const uint32_t batch = B.count;
     // who is served, and the record's shape
-    auto layers_of = [&](uint32_t b) { return (skip && skip[b]) ? 0u : B.b.h_states[b].n_layers; };
-    uint32_t max_layers = 0, served = 0;
+    RecordShape rs{B.log_n, trace_count, 0};
+    uint32_t served = 0;
     for (uint32_t b = 0; b < batch; b++) {
-        const uint32_t nl = layers_of(b);
+        const uint32_t nl = served_layers(B, skip, b);
         if (!nl) continue;
-        if (!chan[b].has_state)
-            return fail(ctx, FRI_EINVAL,
-                        "member " + std::to_string(b) + ": an empty channel state draws no index (channel.rs:65)");
-        max_layers = std::max(max_layers, nl);
+        rs.max_layers = std::max(rs.max_layers, nl);
         served++;
     }
-    auto fri_path_words = [&](uint32_t nl) { return 16 * ((size_t)nl * L - (size_t)nl * (nl ? nl - 1 : 0) / 2); };
-    const size_t tpath_words = (size_t)trace_count * 8 * L;
-    const size_t val_words = trace_count + 2 * (size_t)max_layers;
-    const size_t rec_words = val_words + tpath_words + fri_path_words(max_layers);
-    if (served && (values_stride < val_words || paths_stride < (tpath_words + fri_path_words(max_layers)) * 4)) {
-        paths_len[0] = (tpath_words + fri_path_words(max_layers)) * 4;
+    const size_t val_words = rs.val_words(), rec_words = rs.rec_words();
+    if (served && (values_stride < val_words || paths_stride < rs.path_words(rs.max_layers) * 4)) {
+        paths_len[0] = rs.path_words(rs.max_layers) * 4;
         return fail(ctx, FRI_EINVAL,
                     "record strides too small (values: trace_count + 2 per layer words; paths: see paths_len[0])");
     }
     FRI_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
     // members per chunk: what the byte budget holds, or the hook's count; halved while the staging does not fit
     size_t chunk = B.query_chunk ? B.query_chunk
                                  : std::max<size_t>(QUERY_CHUNK_BYTES / QuerySections(1, Q, rec_words).total, 1);
@@ -600,7 +508,7 @@ extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_
         }
     for (uint32_t b = 0; b < batch; b++) paths_len[b] = 0;
     if (!served) {
-        ctx->err.clear();
+        if (chan) ctx->err.clear();          // (the round leaves the last error's text)
         return FRI_OK;
     }
 
@@ -615,11 +523,11 @@ extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_
     qp.ttree_stride = B.ttree_stride;
     qp.rec_words = rec_words;
     qp.trace_stride = trace_stride;
-    qp.range = max_index + 1;
+    qp.range = range;
     qp.num_queries = Q;
-    qp.log_n = L;
+    qp.log_n = B.log_n;
     qp.trace_count = trace_count;
-    qp.max_layers = max_layers;
+    qp.max_layers = rs.max_layers;
     for (int k = 0; k <= B.lay.rmax + 1; k++) {
         qp.layer_off[k] = (uint32_t)B.lay.layer_off[k];
         qp.tree_off[k] = (uint32_t)B.lay.tree_off[k];
@@ -631,25 +539,29 @@ extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_
         const QuerySections S(m, Q, rec_words);
         fri_channel_state* hchan = reinterpret_cast<fri_channel_state*>(B.h_q + S.chan);
         uint32_t* hnl = reinterpret_cast<uint32_t*>(B.h_q + S.nl);
-        const uint64_t* hidx = reinterpret_cast<const uint64_t*>(B.h_q + S.idx);
+        uint64_t* hidx = reinterpret_cast<uint64_t*>(B.h_q + S.idx);
         const uint32_t* hrec = reinterpret_cast<const uint32_t*>(B.h_q + S.meta);
         bool any = false;
         for (size_t i = 0; i < m; i++) {
-            hchan[i] = chan[b0 + i];
-            hnl[i] = layers_of((uint32_t)(b0 + i));
+            if (chan) hchan[i] = chan[b0 + i];
+            else hidx[i] = idx_in[b0 + i];
+            hnl[i] = served_layers(B, skip, (uint32_t)(b0 + i));
             any = any || hnl[i];
         }
         if (!any) continue;
-        FRI_HIP(ctx, hipMemcpyAsync(dmeta, B.h_q, S.idx, hipMemcpyHostToDevice, s));     // the states and n_layers
+        // up: the phase's states and n_layers (it draws the indices), the round's n_layers and indices
+        const size_t up0 = chan ? S.chan : S.nl, up1 = chan ? S.idx : S.meta;
+        FRI_HIP(ctx, hipMemcpyAsync(dmeta + up0, B.h_q + up0, up1 - up0, hipMemcpyHostToDevice, s));
         qp.n_layers = reinterpret_cast<const uint32_t*>(dmeta + S.nl);
         qp.chan = reinterpret_cast<uint32_t*>(dmeta + S.chan);
         qp.indices = reinterpret_cast<uint64_t*>(dmeta + S.idx);
         qp.out = B.b.words(BB_QOUT);
         qp.first = (uint32_t)b0;
         qp.members = (uint32_t)m;
-        launch_query_phase(qp, s);
+        if (chan) launch_query_chain(qp, s);
+        launch_query_gather(qp, s);
         FRI_HIP(ctx, hipGetLastError());
-        FRI_HIP(ctx, hipMemcpyAsync(B.h_q, dmeta, S.meta, hipMemcpyDeviceToHost, s));
+        if (chan) FRI_HIP(ctx, hipMemcpyAsync(B.h_q, dmeta, S.meta, hipMemcpyDeviceToHost, s));
         FRI_HIP(ctx, hipMemcpyAsync(B.h_q + S.meta, qp.out, S.rec, hipMemcpyDeviceToHost, s));
         // the next chunk reuses the staging
         FRI_HIP(ctx, hipStreamSynchronize(s));
@@ -657,18 +569,59 @@ extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_
             const uint32_t nl = hnl[i];
             if (!nl) continue;
             const size_t b = b0 + i;
-            chan[b] = hchan[i];
+            if (chan) chan[b] = hchan[i];
             for (size_t qi = 0; qi < Q; qi++) {
                 const uint32_t* rec = hrec + (i * Q + qi) * rec_words;
-                uint32_t* v = values + (b * Q + qi) * values_stride;
-                uint8_t* p = paths + (b * Q + qi) * paths_stride;
-                indices[b * Q + qi] = hidx[i * Q + qi];
-                memcpy(v, rec, (trace_count + 2 * (size_t)nl) * 4);
-                memcpy(p, rec + val_words, (tpath_words + fri_path_words(nl)) * 4);
+                if (idx_out) idx_out[b * Q + qi] = hidx[i * Q + qi];
+                memcpy(values + (b * Q + qi) * values_stride, rec, (trace_count + 2 * (size_t)nl) * 4);
+                memcpy(paths + (b * Q + qi) * paths_stride, rec + val_words, rs.path_words(nl) * 4);
             }
-            paths_len[b] = (tpath_words + fri_path_words(nl)) * 4;
+            paths_len[b] = rs.path_words(nl) * 4;
         }
     }
     ctx->err.clear();
     return FRI_OK;
+}
+
+extern "C" int fri_batch_query_round(fri_ctx* ctx, const uint64_t* indices, const uint8_t* skip, uint32_t trace_count,
+                                     uint64_t trace_stride, uint32_t* values, size_t values_stride, uint8_t* paths,
+                                     size_t paths_stride, size_t* paths_len) {
+    if (!ctx || !indices || !values || !paths || !paths_len) return fail(ctx, FRI_EINVAL, "null argument");
+    int rc = query_batch_ok(ctx, trace_count);       // (no batch_ctx_ok: a profiling context serves rounds)
+    if (rc) return rc;
+    const Batch& B = ctx->batch;
+    // (the FRI openings take any index, mod the layer's size, as fri_decommit_query; the trace's do not)
+    for (uint32_t b = 0; trace_count && b < B.count; b++)
+        if (served_layers(B, skip, b) && (indices[b] >> B.log_n))
+            return fail(ctx, FRI_EINVAL, "member " + std::to_string(b) + ": index out of range");
+    return run_queries(ctx, 1, indices, nullptr, 0, skip, trace_count, trace_stride, nullptr, values, values_stride,
+                       paths, paths_stride, paths_len);
+}
+
+extern "C" int fri_batch_query_phase(fri_ctx* ctx, uint32_t num_queries, uint64_t max_index, fri_channel_state* chan,
+                                     const uint8_t* skip, uint32_t trace_count, uint64_t trace_stride,
+                                     uint64_t* indices, uint32_t* values, size_t values_stride, uint8_t* paths,
+                                     size_t paths_stride, size_t* paths_len) {
+    static_assert(sizeof(fri_channel_state) == 36, "k_query_chain reads a channel state as 9 words");
+    if (!ctx || !chan || !paths_len || (num_queries && (!indices || !values || !paths)))
+        return fail(ctx, FRI_EINVAL, "null argument");
+    int rc = batch_ctx_ok(ctx);
+    if (!rc) rc = query_batch_ok(ctx, trace_count);
+    if (rc) return rc;
+    const Batch& B = ctx->batch;
+    if (max_index >> 32) return fail(ctx, FRI_EINVAL, "max_index must be below 2^32");
+    // (the FRI openings take any index, mod the layer's size; the trace's do not)
+    if (trace_count && (max_index >> B.log_n))
+        return fail(ctx, FRI_EINVAL, "max_index must be below 2^log_n with trace_count > 0");
+    if (num_queries > FRI_VERIFY_MAX_QUERIES) return fail(ctx, FRI_EINVAL, "num_queries above FRI_VERIFY_MAX_QUERIES");
+    if (num_queries == 0) {
+        ctx->err.clear();
+        return FRI_OK;
+    }
+    for (uint32_t b = 0; b < B.count; b++)
+        if (served_layers(B, skip, b) && !chan[b].has_state)
+            return fail(ctx, FRI_EINVAL,
+                        "member " + std::to_string(b) + ": an empty channel state draws no index (channel.rs:65)");
+    return run_queries(ctx, num_queries, nullptr, chan, max_index + 1, skip, trace_count, trace_stride, indices, values,
+                       values_stride, paths, paths_stride, paths_len);
 }

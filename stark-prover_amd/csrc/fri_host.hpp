@@ -133,8 +133,8 @@ enum {
     BB_TROOTS,    // the trace trees' roots, 8 words per member
     BB_CP,        // composition polynomial on the coset, n words per member
     BB_FIB,       // one FibsqMember per member
-    BB_QMETA,     // fri_batch_query_round: one BatchQueryMember per member
-    BB_QOUT,      // ... and the members' records
+    BB_QMETA,     // the query round and phase: a chunk's states, n_layers and indices
+    BB_QOUT,      // ... and its records
     BB_N
 };
 struct BatchBufs {
@@ -164,7 +164,7 @@ struct Batch {
     // pinned staging of the query rounds and the trace roots (grown on demand)
     uint8_t* h_q = nullptr;
     size_t h_q_cap = 0;
-    uint32_t query_chunk = 0;    // fri_debug_set_query_chunk: members per chunk of fri_batch_query_phase (0: by byte budget)
+    uint32_t query_chunk = 0;    // fri_debug_set_query_chunk: members per chunk of the query round and phase (0: by byte budget)
 };
 
 // The batched verifier (fri_verify_batch, fri_verify.hip): one device buffer
@@ -620,6 +620,18 @@ inline void digest_to_bytes(const uint32_t* w, uint8_t* out) {
         out[4 * i + 2] = (uint8_t)(w[i] >> 8); out[4 * i + 3] = (uint8_t)w[i];
     }
 }
+
+// The sizes of a query record in words (k_batch_query_all, fri_prover.hip, has
+// the layout): what the batch's query round and phase write and the batched
+// verifier reads.  A member with nl <= max_layers layers fills path_words(nl).
+struct RecordShape {
+    uint32_t log_n, trace_count, max_layers;
+    size_t val_words() const { return trace_count + 2 * (size_t)max_layers; }
+    size_t tpath_words() const { return (size_t)trace_count * 8 * log_n; }
+    size_t fri_path_words(uint32_t nl) const { return 16 * ((size_t)nl * log_n - (size_t)nl * (nl ? nl - 1 : 0) / 2); }
+    size_t path_words(uint32_t nl) const { return tpath_words() + fri_path_words(nl); }
+    size_t rec_words() const { return val_words() + path_words(max_layers); }
+};
 
 // ---- fri_ctx.hip: timed spans of profiled commits (hipEvents on ctx->stream)
 size_t span_begin(fri_ctx* ctx, const char* cls, uint64_t bytes);

@@ -49,6 +49,16 @@ struct DevState {
 __host__ __device__ inline size_t level_offset(uint32_t L, uint32_t l) {
     return ((size_t)2 << L) - ((size_t)2 << (L - l));
 }
+// What an authentication path takes at level l: the sibling of `leaf`'s
+// ancestor there, in a tree of 2^D leaves; and its eight words stored as the
+// big-endian bytes a path is sent as.
+__device__ __forceinline__ const uint32_t* sibling_digest(const uint32_t* tree, uint32_t D, uint32_t l, uint64_t leaf) {
+    return tree + 8 * (level_offset(D, l) + ((leaf >> l) ^ 1u));
+}
+__device__ __forceinline__ void store_digest_be(uint32_t* o, const uint32_t* d) {
+#pragma unroll
+    for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+}
 
 // ---- launchers (fri_kernels.hip); all asynchronous on `s` ----------------
 struct NttPlan {
@@ -339,43 +349,24 @@ void launch_fibsq_cp_batch(const uint32_t* f_lde, size_t f_stride, uint32_t* out
 // out[j] = lde[(index + j*stride) mod 2^L], then count paths of L big-endian digests
 void launch_trace_gather(const uint32_t* lde, const uint32_t* tree, uint32_t L, uint64_t index, uint64_t stride,
                          uint32_t count, uint32_t* out, hipStream_t s);
-// One query of every member of a batch, one launch (fri_batch_query_round;
-// k_batch_query has the record's layout).  mem[b].n_layers = 0 leaves member b out.
-struct BatchQueryMember {
-    uint64_t index;
-    uint32_t n_layers, pad;
-};
-struct BatchQuery {
+// The queries of `members` members of the resident batch, from member `first`
+// on.  fri_batch_query_phase: k_query_chain draws every index from the member's
+// channel and absorbs the openings from the resident buffers
+// (launch_query_chain), then k_batch_query_all gathers the records
+// (launch_query_gather), both on `s`.  fri_batch_query_round: the gather alone,
+// of one query whose indices the host uploaded.  The per-member arrays are the
+// chunk's (member first + m at m); n_layers[m] = 0 leaves a member out.
+struct QueryPhase {
     const uint32_t* layers;      // the FRI batch (BatchTask's slices and offsets)
     const uint32_t* trees;
     size_t lay_stride, tre_stride;
     const uint32_t* tlde;        // the trace batch (trace_count > 0)
     const uint32_t* ttree;
     size_t tlde_stride, ttree_stride;
-    const BatchQueryMember* mem;
-    uint32_t* out;
-    size_t rec_words;
-    uint64_t trace_stride;
-    uint32_t log_n, trace_count, max_layers;
-    uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2];
-};
-void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s);
-// The whole query phase of `members` members of the resident batch, from member
-// `first` on (fri_batch_query_phase): k_query_chain draws every index from the
-// member's channel and absorbs the openings from the resident buffers, then
-// k_batch_query_all gathers the records, both on `s`.  The per-member arrays
-// are the chunk's (member first + m at m); n_layers[m] = 0 leaves a member out.
-struct QueryPhase {
-    const uint32_t* layers;      // the resident batch, as BatchQuery
-    const uint32_t* trees;
-    size_t lay_stride, tre_stride;
-    const uint32_t* tlde;
-    const uint32_t* ttree;
-    size_t tlde_stride, ttree_stride;
     const uint32_t* n_layers;    // [members]
     uint32_t* chan;              // [members] fri_channel_state, 9 words: in, and out after the last send
-    uint64_t* indices;           // [members][num_queries] out
-    uint32_t* out;               // [members][num_queries] records of rec_words words (k_batch_query's)
+    uint64_t* indices;           // [members][num_queries]: the chain's output, the gather's input
+    uint32_t* out;               // [members][num_queries] records of rec_words words (k_batch_query_all has the layout)
     size_t rec_words;
     uint64_t trace_stride;
     uint64_t range;              // max_index + 1, <= 2^32
@@ -383,7 +374,8 @@ struct QueryPhase {
     uint32_t log_n, trace_count, max_layers;
     uint32_t layer_off[BATCH_MAX_LOG + 2], tree_off[BATCH_MAX_LOG + 2];
 };
-void launch_query_phase(const QueryPhase& q, hipStream_t s);
+void launch_query_chain(const QueryPhase& q, hipStream_t s);
+void launch_query_gather(const QueryPhase& q, hipStream_t s);
 
 // Proof-of-work grinding (fri_grind, fri_grind_batch): the
 // smallest nonce whose send leaves the channel state with leading zero bits.

@@ -880,16 +880,10 @@ __global__ void k_decommit_gather(const uint32_t* __restrict__ layers, const uin
             continue;
         }
         const uint32_t* d;
-        if (!sharded) {
-            d = tr + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
-        } else if (l < lb) {                         // inside the block: the block-local tree
-            d = tr + 8 * (level_offset(lb, l) + (((leaf & bmask) >> l) ^ 1u));
-        } else {                                     // above it: the replicated top tree of block roots
-            const uint32_t t = l - lb;
-            d = top + dp.top_off[k] + 8 * (level_offset(dp.logG, t) + (((leaf >> lb) >> t) ^ 1u));
-        }
-#pragma unroll
-        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+        if (!sharded) d = sibling_digest(tr, L, l, leaf);
+        else if (l < lb) d = sibling_digest(tr, lb, l, leaf & bmask);               // inside the block: its own tree
+        else d = sibling_digest(top + dp.top_off[k], dp.logG, l - lb, leaf >> lb);  // above it: the tree of block roots
+        store_digest_be(o, d);
     }
 }
 void launch_decommit_gather(const uint32_t* layers, const uint32_t* trees, const DecommitPlan& dp, uint32_t* out,

@@ -108,10 +108,8 @@ __global__ void k_trace_gather(const uint32_t* __restrict__ lde, const uint32_t*
     if (threadIdx.x == 0) out[j] = lde[leaf];
     const uint32_t l = threadIdx.x;
     if (l >= L) return;
-    const uint32_t* d = tree + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
-    uint32_t* o = out + count + (size_t)j * 8 * L + 8 * l;
-#pragma unroll
-    for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+    const uint32_t* d = sibling_digest(tree, L, l, leaf);
+    store_digest_be(out + count + (size_t)j * 8 * L + 8 * l, d);
 }
 
 void launch_trace_gather(const uint32_t* lde, const uint32_t* tree, uint32_t L, uint64_t index, uint64_t stride,
@@ -119,66 +117,12 @@ void launch_trace_gather(const uint32_t* lde, const uint32_t* tree, uint32_t L, 
     hipLaunchKernelGGL(k_trace_gather, dim3(count), dim3(64), 0, s, lde, tree, L, index, stride, out, count);
 }
 
-// One query of every member of a batch (fri_batch_query_round): block
-// (x, member), lane l = tree level l.  x < trace_count opens the member's trace
-// LDE at index + x * trace_stride (k_trace_gather's value and path); above,
-// x - trace_count is a FRI layer k of the member: the values at idx = index mod
-// m_k and its sibling and their two paths (k_decommit_gather).  A member's
-// record is rec_words words at out + member * rec_words:
-//   [trace values][2 * max_layers FRI values][trace paths, 8 L words each]
-//   [FRI paths, layer k's two at 16 (k L - k (k - 1) / 2)]
-// of which a member with fewer layers fills a prefix of each part.  A member
-// with n_layers = 0 in mem (skipped, or its commit failed) writes nothing.
-__global__ __launch_bounds__(64) void k_batch_query(BatchQuery q) {
-    const uint32_t x = blockIdx.x, l = threadIdx.x;
-    const size_t b = blockIdx.y;
-    const BatchQueryMember m = q.mem[b];
-    if (m.n_layers == 0) return;
-    const uint32_t L = q.log_n, tc = q.trace_count;
-    uint32_t* rec = q.out + b * q.rec_words;
-    uint32_t* tpaths = rec + tc + 2 * q.max_layers;
-    if (x < tc) {
-        const uint64_t leaf = (m.index + x * q.trace_stride) & (((uint64_t)1 << L) - 1);
-        if (l == 0) rec[x] = q.tlde[b * q.tlde_stride + leaf];
-        if (l >= L) return;
-        const uint32_t* d = q.ttree + b * q.ttree_stride + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
-        uint32_t* o = tpaths + (size_t)x * 8 * L + 8 * l;
-#pragma unroll
-        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
-        return;
-    }
-    const uint32_t k = x - tc;
-    if (k >= m.n_layers) return;
-    const uint32_t Lk = L - k;
-    const uint64_t mk = (uint64_t)1 << Lk;
-    const uint64_t idx = m.index % mk, sib = (idx + mk / 2) % mk;
-    const uint32_t* lay = q.layers + b * q.lay_stride + q.layer_off[k];
-    if (l == 0) {
-        rec[tc + 2 * k] = lay[idx];
-        rec[tc + 2 * k + 1] = lay[sib];
-    }
-    if (l >= Lk) return;
-    const uint32_t* tr = q.trees + b * q.tre_stride + q.tree_off[k];
-    uint32_t* paths = tpaths + (size_t)tc * 8 * L + 16 * ((size_t)k * L - (size_t)k * (k - 1) / 2);
-#pragma unroll
-    for (int which = 0; which < 2; which++) {
-        const uint64_t leaf = which ? sib : idx;
-        const uint32_t* d = tr + 8 * (level_offset(Lk, l) + ((leaf >> l) ^ 1u));
-        uint32_t* o = paths + (size_t)which * 8 * Lk + 8 * l;
-#pragma unroll
-        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
-    }
-}
-
-void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s) {
-    hipLaunchKernelGGL(k_batch_query, dim3(q.trace_count + q.max_layers, batch), dim3(64), 0, s, q);
-}
-
 // ------------------------------------------------ the query phase (device) ---
 // fri_batch_query_phase: every query of every member of a batch, the members'
 // channels included.  The verifier's split, turned around:
 // k_query_chain runs each member's Fiat-Shamir chain and leaves the indices it
 // drew, then k_batch_query_all gathers the records of those indices.
+// fri_batch_query_round is that gather alone, of one query at the host's indices.
 
 // One lane per member, workgroups of one wave (k_verify_chain's shape).  The
 // lane runs num_queries x { receive_random_int(0, range - 1, true), then the
@@ -187,7 +131,7 @@ void launch_batch_query(const BatchQuery& q, uint32_t batch, hipStream_t s) {
 //   (value, path, sibling value, sibling path), a one-element layer's value
 //   once more first (fri_commit.rs:147-149).
 // Values and sibling digests are read where they live, in the member's trace
-// LDE and tree and its layers and trees (k_batch_query's addressing); nothing
+// LDE and tree and its layers and trees (k_batch_query_all's addressing); nothing
 // is staged.  Every address is formed from the drawn index masked to the
 // layer's size.  Lanes past their member's last layer sit the unit out; a
 // member with n_layers = 0 is left out and nothing of it is written.
@@ -247,10 +191,18 @@ __global__ __launch_bounds__(64) void k_query_chain(QueryPhase q) {
     chan[8] = has;
 }
 
-// k_batch_query with a query dimension: block (x + openings * query, member),
-// lane l = tree level l, the index the one k_query_chain drew.  The record of
-// (member, query), rec_words words at out + (member * num_queries + query) *
-// rec_words, is k_batch_query's.
+// The openings of every (member, query): block (x + openings * query, member),
+// lane l = tree level l, the index the one in q.indices.  x < trace_count opens
+// the member's trace LDE at index + x * trace_stride (k_trace_gather's value and
+// path); above, x - trace_count is a FRI layer k of the member: the values at
+// idx = index mod m_k and its sibling and their two paths (k_decommit_gather).
+// THE RECORD of (member, query) is rec_words words at out + (member *
+// num_queries + query) * rec_words:
+//   [trace values][2 * max_layers FRI values][trace paths, 8 L words each]
+//   [FRI paths, layer k's two at 16 (k L - k (k - 1) / 2)]
+// of which a member with fewer layers fills a prefix of each part (the sizes:
+// RecordShape, fri_host.hpp).  A member with n_layers = 0 (skipped, or its
+// commit failed) writes nothing.
 __global__ __launch_bounds__(64) void k_batch_query_all(QueryPhase q) {
     const uint32_t L = q.log_n, tc = q.trace_count, opens = tc + q.max_layers;
     const uint32_t x = blockIdx.x % opens, qi = blockIdx.x / opens, l = threadIdx.x;
@@ -265,10 +217,8 @@ __global__ __launch_bounds__(64) void k_batch_query_all(QueryPhase q) {
         const uint64_t leaf = (index + x * q.trace_stride) & (((uint64_t)1 << L) - 1);
         if (l == 0) rec[x] = q.tlde[b * q.tlde_stride + leaf];
         if (l >= L) return;
-        const uint32_t* d = q.ttree + b * q.ttree_stride + 8 * (level_offset(L, l) + ((leaf >> l) ^ 1u));
-        uint32_t* o = tpaths + (size_t)x * 8 * L + 8 * l;
-#pragma unroll
-        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+        const uint32_t* d = sibling_digest(q.ttree + b * q.ttree_stride, L, l, leaf);
+        store_digest_be(tpaths + (size_t)x * 8 * L + 8 * l, d);
         return;
     }
     const uint32_t k = x - tc;
@@ -286,17 +236,17 @@ __global__ __launch_bounds__(64) void k_batch_query_all(QueryPhase q) {
     uint32_t* paths = tpaths + (size_t)tc * 8 * L + 16 * ((size_t)k * L - (size_t)k * (k - 1) / 2);
 #pragma unroll
     for (int which = 0; which < 2; which++) {
-        const uint64_t leaf = which ? sib : idx;
-        const uint32_t* d = tr + 8 * (level_offset(Lk, l) + ((leaf >> l) ^ 1u));
-        uint32_t* o = paths + (size_t)which * 8 * Lk + 8 * l;
-#pragma unroll
-        for (int w = 0; w < 8; w++) o[w] = __builtin_bswap32(d[w]);
+        const uint32_t* d = sibling_digest(tr, Lk, l, which ? sib : idx);
+        store_digest_be(paths + (size_t)which * 8 * Lk + 8 * l, d);
     }
 }
 
-void launch_query_phase(const QueryPhase& q, hipStream_t s) {
+void launch_query_chain(const QueryPhase& q, hipStream_t s) {
     if (!q.members || !q.num_queries) return;
     hipLaunchKernelGGL(k_query_chain, dim3((q.members + 63u) / 64u), dim3(64), 0, s, q);
+}
+void launch_query_gather(const QueryPhase& q, hipStream_t s) {
+    if (!q.members || !q.num_queries) return;
     hipLaunchKernelGGL(k_batch_query_all, dim3((q.trace_count + q.max_layers) * q.num_queries, q.members), dim3(64), 0,
                        s, q);
 }

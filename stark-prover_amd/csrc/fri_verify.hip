@@ -96,8 +96,8 @@ extern "C" int fri_verify_batch_pow(fri_ctx* ctx, const fri_verify_shape* shape,
     }
     if (batch < 1 || batch > 65535) return fail(ctx, FRI_EINVAL, "batch must be 1..65535");
     if (Q && (!indices || !values || !paths)) return fail(ctx, FRI_EINVAL, "null argument");
-    const size_t hw = (tc ? 11 : 0) + 9 * (size_t)ML, vw = tc + 2 * (size_t)ML;
-    const size_t pw = (size_t)tc * 8 * L + 16 * ((size_t)ML * L - (size_t)ML * (ML - 1) / 2);
+    const RecordShape rs{L, tc, ML};
+    const size_t hw = (tc ? 11 : 0) + 9 * (size_t)ML, vw = rs.val_words(), pw = rs.path_words(ML);
     if (head_stride < hw || (Q && (values_stride < vw || paths_stride < pw * 4)))
         return fail(ctx, FRI_EINVAL,
                     "record strides too small (head: [11 +] 9 max_layers words; values: trace_count + 2 max_layers "

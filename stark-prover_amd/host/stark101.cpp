@@ -663,22 +663,72 @@ void decommit_fri(size_t num_queries, size_t max_index, const FRIProof& proof, F
 }
 
 namespace {
-// One fri_batch_query_round on `gpu` for members of `n_layers[b]` layers, then
-// every channel absorbs its record: trace_count (value, path) pairs, then the
-// layers' openings as decommit_query sends them.
-void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_layers,
-                 const std::vector<uint64_t>& indices, uint32_t trace_count, uint64_t trace_stride,
-                 std::vector<FriChannel>& channels) {
-    const size_t B = channels.size(), tpath = 32 * size_t{log_n};
+// The sizes of a query record (fri_batch_query_round, fri_amd.h, has the
+// layout) of a member with `layers` layers: its values in words, its paths in
+// bytes (trace_count of log_n digests, then layer k's two of log_n - k).
+struct RecordShape {
+    uint32_t log_n, trace_count;
+    size_t val_words(size_t layers) const { return trace_count + 2 * layers; }
+    size_t path_bytes(size_t layers) const {
+        size_t n = size_t{trace_count} * 32 * log_n;
+        for (size_t k = 0; k < layers; k++) n += 64 * (log_n - k);
+        return n;
+    }
+};
+
+// One record's messages in the transcript's order, each to sink(bytes, len):
+// trace_count (value, path) pairs, then per layer (value, path, sibling value,
+// sibling path) as decommit_query sends them, a one-element layer's value once
+// more first (fri_commit.rs:147-149).
+template <class Sink>
+void walk_record(const uint32_t* values, const uint8_t* paths, const RecordShape& shape, size_t n_layers, Sink&& sink) {
+    const size_t tc = shape.trace_count, tpath = 32 * size_t{shape.log_n};
+    auto value = [&](uint32_t v) {
+        const auto m = FriChannel::be64(v);
+        sink(m.data(), m.size());
+    };
+    for (size_t j = 0; j < tc; j++) {
+        value(values[j]);
+        sink(paths + j * tpath, tpath);
+    }
+    size_t off = tc * tpath;
+    for (size_t k = 0; k < n_layers; k++) {
+        const size_t pb = 32 * size_t{shape.log_n - k};
+        if (pb == 0) value(values[tc + 2 * k]);
+        value(values[tc + 2 * k]);
+        sink(paths + off, pb);
+        value(values[tc + 2 * k + 1]);
+        sink(paths + off + pb, pb);
+        off += 2 * pb;
+    }
+}
+
+// What both calls below start with: the resident batch has one member per
+// channel (else `mismatch`), and the records' strides hold the most layers.
+struct RecordStrides {
+    RecordShape shape;
+    size_t vstride, pstride;
+};
+RecordStrides record_strides(const Gpu& gpu, size_t B, const char* mismatch, uint32_t log_n,
+                             const std::vector<size_t>& n_layers, uint32_t trace_count) {
     uint64_t generation = 0;
     uint32_t members = 0, resident_log_n = 0;
     gpu.check(fri_batch_info(gpu.ctx(), &generation, &members, &resident_log_n), "fri_batch_info");
-    if (members != B) throw Panic("fri_batch_query_round: one index per member of the resident batch");
+    if (members != B) throw Panic(mismatch);
     size_t max_layers = 0;
     for (size_t nl : n_layers) max_layers = std::max(max_layers, nl);
-    size_t fri_bytes = 0;
-    for (size_t k = 0; k < max_layers; k++) fri_bytes += 2 * 32 * (log_n - k);
-    const size_t vstride = trace_count + 2 * max_layers, pstride = std::max<size_t>(trace_count * tpath + fri_bytes, 1);
+    const RecordShape shape{log_n, trace_count};
+    return {shape, shape.val_words(max_layers), std::max<size_t>(shape.path_bytes(max_layers), 1)};
+}
+
+// One fri_batch_query_round on `gpu` for members of `n_layers[b]` layers, then
+// every channel absorbs its record (walk_record).
+void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_layers,
+                 const std::vector<uint64_t>& indices, uint32_t trace_count, uint64_t trace_stride,
+                 std::vector<FriChannel>& channels) {
+    const size_t B = channels.size();
+    const auto [shape, vstride, pstride] = record_strides(
+        gpu, B, "fri_batch_query_round: one index per member of the resident batch", log_n, n_layers, trace_count);
     std::vector<uint32_t> values(B * vstride);
     std::vector<uint8_t> paths(B * pstride);
     std::vector<size_t> got(B, 0);
@@ -686,27 +736,11 @@ void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_la
                                     paths.data(), pstride, got.data()),
               "fri_batch_query_round");
     for (size_t b = 0; b < B; b++) {
-        const uint32_t* v = values.data() + b * vstride;
-        const uint8_t* p = paths.data() + b * pstride;
-        size_t want = trace_count * tpath;
-        for (size_t k = 0; k < n_layers[b]; k++) want += 2 * 32 * (log_n - k);
-        if (got[b] != want) throw Panic("fri_batch_query_round: member " + std::to_string(b) + " was not served");
+        if (got[b] != shape.path_bytes(n_layers[b]))
+            throw Panic("fri_batch_query_round: member " + std::to_string(b) + " was not served");
         FriChannel& ch = channels[b];
-        for (size_t j = 0; j < trace_count; j++) {
-            ch.send(FE(v[j]).to_bytes());
-            ch.send(p + j * tpath, tpath);
-        }
-        size_t off = trace_count * tpath;
-        for (size_t k = 0; k < n_layers[b]; k++) {
-            const size_t depth = log_n - k, pb = 32 * depth;
-            auto val = FE(v[trace_count + 2 * k]).to_bytes(), sval = FE(v[trace_count + 2 * k + 1]).to_bytes();
-            if (depth == 0) ch.send(val);            // fri_commit.rs:147-149: length == 1 sends it first
-            ch.send(val);
-            ch.send(p + off, pb);
-            ch.send(sval);
-            ch.send(p + off + pb, pb);
-            off += 2 * pb;
-        }
+        walk_record(values.data() + b * vstride, paths.data() + b * pstride, shape, n_layers[b],
+                    [&ch](const uint8_t* m, size_t len) { ch.send(m, len); });
     }
 }
 
@@ -718,19 +752,12 @@ void query_round(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_la
 std::vector<std::vector<uint64_t>> query_phase(const Gpu& gpu, uint32_t log_n, const std::vector<size_t>& n_layers,
                                                size_t num_queries, uint64_t max_index, uint32_t trace_count,
                                                uint64_t trace_stride, std::vector<FriChannel>& channels) {
-    const size_t B = channels.size(), Q = num_queries, tpath = 32 * size_t{log_n};
+    const size_t B = channels.size(), Q = num_queries;
     std::vector<std::vector<uint64_t>> out(B);
     if (Q == 0) return out;
-    uint64_t generation = 0;
-    uint32_t members = 0, resident_log_n = 0;
-    gpu.check(fri_batch_info(gpu.ctx(), &generation, &members, &resident_log_n), "fri_batch_info");
-    if (members != B) throw Panic("fri_batch_query_phase: one channel per member of the resident batch");
+    const auto [shape, vstride, pstride] = record_strides(
+        gpu, B, "fri_batch_query_phase: one channel per member of the resident batch", log_n, n_layers, trace_count);
     if (Q >> 32) throw Panic("fri_batch_query_phase: num_queries out of range");
-    size_t max_layers = 0;
-    for (size_t nl : n_layers) max_layers = std::max(max_layers, nl);
-    size_t fri_bytes = 0;
-    for (size_t k = 0; k < max_layers; k++) fri_bytes += 2 * 32 * (log_n - k);
-    const size_t vstride = trace_count + 2 * max_layers, pstride = std::max<size_t>(trace_count * tpath + fri_bytes, 1);
     std::vector<fri_channel_state> chan(B);
     for (size_t b = 0; b < B; b++) {
         if (channels[b].state.size() != 64) throw Panic("Channel state is not valid hex");     // channel.rs:65
@@ -747,35 +774,18 @@ std::vector<std::vector<uint64_t>> query_phase(const Gpu& gpu, uint32_t log_n, c
                                     got.data()),
               "fri_batch_query_phase");
     for (size_t b = 0; b < B; b++) {
-        size_t want = trace_count * tpath;
-        for (size_t k = 0; k < n_layers[b]; k++) want += 2 * 32 * (log_n - k);
-        if (got[b] != want) throw Panic("fri_batch_query_phase: member " + std::to_string(b) + " was not served");
+        if (got[b] != shape.path_bytes(n_layers[b]))
+            throw Panic("fri_batch_query_phase: member " + std::to_string(b) + " was not served");
         FriChannel& ch = channels[b];
-        auto put = [&ch](std::vector<uint8_t> m) {
-            ch.compressed_proof.push_back(m);
-            ch.proof.push_back(std::move(m));
+        auto put = [&ch](const uint8_t* m, size_t len) {
+            ch.compressed_proof.emplace_back(m, m + len);
+            ch.proof.emplace_back(m, m + len);
         };
-        auto bytes = [](const uint8_t* p, size_t len) { return std::vector<uint8_t>(p, p + len); };
         for (size_t q = 0; q < Q; q++) {
-            const uint32_t* v = values.data() + (b * Q + q) * vstride;
-            const uint8_t* p = paths.data() + (b * Q + q) * pstride;
             out[b].push_back(indices[b * Q + q]);
             ch.proof.push_back(FriChannel::be64(indices[b * Q + q]));
-            for (size_t j = 0; j < trace_count; j++) {
-                put(FriChannel::be64(v[j]));
-                put(bytes(p + j * tpath, tpath));
-            }
-            size_t off = trace_count * tpath;
-            for (size_t k = 0; k < n_layers[b]; k++) {
-                const size_t depth = log_n - k, pb = 32 * depth;
-                auto val = FriChannel::be64(v[trace_count + 2 * k]), sval = FriChannel::be64(v[trace_count + 2 * k + 1]);
-                if (depth == 0) put(val);                // fri_commit.rs:147-149: length == 1 sends it first
-                put(val);
-                put(bytes(p + off, pb));
-                put(sval);
-                put(bytes(p + off + pb, pb));
-                off += 2 * pb;
-            }
+            walk_record(values.data() + (b * Q + q) * vstride, paths.data() + (b * Q + q) * pstride, shape, n_layers[b],
+                        put);
         }
         ch.state = sha::hex(chan[b].digest, 32);
     }
@@ -1286,9 +1296,8 @@ Packed pack_batch(const std::vector<Msgs>& t, uint32_t log_n, const std::vector<
     pk.sh.offset = static_cast<uint32_t>(offset.value());
     pk.sh.max_index = max_index;
     pk.hw = (tc ? 11 : 0) + 9 * ML;
-    pk.vw = tc + 2 * ML;
-    pk.pb = size_t{tc} * 32 * log_n;
-    for (size_t k = 0; k < ML; k++) pk.pb += 64 * (log_n - k);
+    pk.vw = RecordShape{log_n, tc}.val_words(ML);
+    pk.pb = RecordShape{log_n, tc}.path_bytes(ML);
     const size_t Q = num_queries;
     pk.chan.assign(B, fri_channel_state{});
     pk.n_layers.assign(B, 1);

@@ -658,7 +658,7 @@ class Context:
     def batch_decommit_query(self, member: int, index: int, n_layers: int, log_n: int):
         """fri_batch_decommit_query: decommit_query's tuples for one member."""
         vals = np.empty(2 * n_layers, dtype=np.uint32)
-        total = sum(64 * (log_n - k) for k in range(n_layers))
+        total = record_paths_len(log_n, 0, n_layers)
         buf = ctypes.create_string_buffer(max(total, 1))
         ln = ctypes.c_size_t()
         self._check(self.lib.fri_batch_decommit_query(self.h, member, index, _ptr(vals), vals.size, buf, total,
@@ -736,7 +736,7 @@ class Context:
         if values is None:
             values = np.zeros((batch, trace_count + 2 * nl), dtype=np.uint32)
         if paths is None:
-            paths = np.zeros((batch, max(32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(nl)), 1)),
+            paths = np.zeros((batch, max(record_paths_len(log_n, trace_count, nl), 1)),
                              dtype=np.uint8)
         if values.dtype != np.uint32 or paths.dtype != np.uint8 or values.ndim != 2 or paths.ndim != 2 or \
                 values.shape[0] != batch or paths.shape[0] != batch or not values.flags["C_CONTIGUOUS"] or \
@@ -793,7 +793,7 @@ class Context:
         if values is None:
             values = np.zeros((batch, q, trace_count + 2 * nl), dtype=np.uint32)
         if paths is None:
-            paths = np.zeros((batch, q, max(32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(nl)), 1)),
+            paths = np.zeros((batch, q, max(record_paths_len(log_n, trace_count, nl), 1)),
                              dtype=np.uint8)
         if indices.dtype != np.uint64 or values.dtype != np.uint32 or paths.dtype != np.uint8 or \
                 indices.shape != (batch, q) or values.ndim != 3 or paths.ndim != 3 or \
@@ -815,7 +815,8 @@ class Context:
 
     def set_query_chunk(self, members: int):
         """fri_debug_set_query_chunk: members per staging chunk of later
-        batch_query_phase calls (0: chosen by the staging budget)."""
+        batch_query_round and batch_query_phase calls (0: chosen by the
+        staging budget)."""
         self._check(self.lib.fri_debug_set_query_chunk(self.h, members))
 
     def grind(self, state: Optional[bytes], bits: int, first: int = 0, last: int = 2 ** 64 - 1):
@@ -987,7 +988,7 @@ class Context:
         if n_layers != self.commit_info()[2]:
             raise FriError(FRI_ESTATE, "layer count differs from the resident commit")
         vals = np.empty(2 * n_layers, dtype=np.uint32)
-        total = sum(64 * (log_n - k) for k in range(n_layers))
+        total = record_paths_len(log_n, 0, n_layers)
         buf = ctypes.create_string_buffer(max(total, 1))
         ln = ctypes.c_size_t()
         fn = self.lib.fri_decommit_query_sharded if sharded else self.lib.fri_decommit_query
@@ -1968,13 +1969,20 @@ def fri_commit_batch(polys: Sequence[Sequence[int]], log_n: int, channels: Seque
     return out
 
 
+def record_paths_len(log_n: int, trace_count: int, n_layers: int) -> int:
+    """Bytes of the paths of one query record (fri_batch_query_round's) of a
+    member with n_layers layers: trace_count paths of log_n digests, then layer
+    k's two of log_n - k.  Its values are trace_count + 2 * n_layers words."""
+    return trace_count * 32 * log_n + sum(64 * (log_n - k) for k in range(n_layers))
+
+
 def batch_round_records(values: np.ndarray, paths: np.ndarray, paths_len: int, trace_count: int, n_layers: int,
                         log_n: int):
     """One member's record of Context.batch_query_round (its rows of values
     and paths, the bytes written) taken apart: ([(trace value, path)] *
     trace_count, decommit_query's tuples for the member's n_layers)."""
     tl = 32 * log_n
-    if paths_len != trace_count * tl + sum(64 * (log_n - k) for k in range(n_layers)):
+    if paths_len != record_paths_len(log_n, trace_count, n_layers):
         raise FriError(FRI_ESTATE, "the record does not hold this many layers (a skipped or failed member?)")
     raw = paths[:paths_len].tobytes()
     trace = [(int(values[j]), raw[j * tl:(j + 1) * tl]) for j in range(trace_count)]
@@ -1982,13 +1990,14 @@ def batch_round_records(values: np.ndarray, paths: np.ndarray, paths_len: int, t
 
 
 def query_phase_messages(indices, values: np.ndarray, paths: np.ndarray, n_layers: int, log_n: int,
-                         trace_count: int) -> List[bytes]:
+                         trace_count: int, paths_len: Optional[int] = None) -> List[bytes]:
     """One member's rows of Context.batch_query_phase (its Q indices, (Q,
     stride) values and paths) as the messages of its query phase, in the
     transcript's order: per query be64(index), trace_count x (value, path),
     then per layer what _send_openings sends (a one-element layer's value
-    once more first)."""
-    plen = trace_count * 32 * log_n + sum(64 * (log_n - k) for k in range(n_layers))
+    once more first).  ``paths_len``: the bytes the call wrote per query, when
+    batch_round_records is to check them against n_layers."""
+    plen = record_paths_len(log_n, trace_count, n_layers) if paths_len is None else paths_len
     out: List[bytes] = []
     for q, index in enumerate(indices):
         out.append(int(index).to_bytes(8, "big"))
@@ -2017,10 +2026,8 @@ def _device_query_phase(ctx: "Context", num_queries: int, max_index: int, fris: 
     if num_queries == 0:
         return [[] for _ in fris]
     for b, (p, ch) in enumerate(zip(fris, channels)):
-        if lens[b] != trace_count * 32 * log_n + sum(64 * (log_n - k) for k in range(p.n_layers)):
-            raise FriError(FRI_ESTATE, "the record does not hold this many layers (a skipped or failed member?)")
-        ch.take_over_queries(query_phase_messages(idx[b], values[b], paths[b], p.n_layers, log_n, trace_count),
-                             num_queries, out[b].hex())
+        ch.take_over_queries(query_phase_messages(idx[b], values[b], paths[b], p.n_layers, log_n, trace_count,
+                                                  lens[b]), num_queries, out[b].hex())
     return [[int(i) for i in idx[b]] for b in range(len(fris))]
 
 
@@ -2166,7 +2173,7 @@ def verify_record_strides(log_n: int, max_layers: int, trace_count: int) -> tupl
     """(head words, values words, paths bytes) of one member's head and of one
     (member, query) record: the query record is fri_batch_query_round's."""
     return ((11 if trace_count else 0) + 9 * max_layers, trace_count + 2 * max_layers,
-            32 * log_n * trace_count + sum(64 * (log_n - k) for k in range(max_layers)))
+            record_paths_len(log_n, trace_count, max_layers))
 
 
 def pack_transcripts(transcripts: Sequence[Sequence[bytes]], log_n: int, n_layers: Sequence[int], num_queries: int,

@@ -342,3 +342,69 @@ def test_outputs_feed_the_batched_verifier(ctx):
     verdict = ctx.verify_batch(shape, B, np.zeros((B, 36), dtype=np.uint8), np.array(nls, dtype=np.uint32), a_last,
                                head, hw, idx, values, vw, paths, pb)
     assert verdict[5] and not np.delete(verdict, 5).any()
+
+
+# ---- 7. the round stages through the same chunks ------------------------------------
+def _fri_only_round_case(ctx, oracle):
+    log_n = 7
+    polys = [oracle.splitmix64_np(70 + b, d).astype(np.uint32) for b, d in enumerate([16, 16, 3, 16, 16])]
+    res, _ = _commit(ctx, polys, log_n)
+    nls = [r.n_layers for r in res]
+    assert len(set(nls)) > 1
+    return log_n, max(nls), dict(indices=[5, 77, (1 << 40) + 3, 9, 127], skip=[0, 0, 0, 1, 0])
+
+
+def _trace_round_case(ctx, oracle):
+    chans = [fri_amd.Channel() for _ in range(5)]
+    proofs = fri_amd.prove_fibsq_batch([3, 4, 5, 6, 7], 4, 2, 0, chans, ctx=ctx)
+    return 6, max(p.fri.n_layers for p in proofs), dict(indices=[0, 17, 55, 3, 63], trace_count=3, trace_stride=4)
+
+
+@pytest.mark.parametrize("case", [_fri_only_round_case, _trace_round_case])
+def test_round_chunks_give_the_same_bytes(ctx, oracle, case):
+    log_n, ml, kw = case(ctx, oracle)
+    tc, skip = kw.get("trace_count", 0), kw.get("skip", [0] * 5)
+
+    def run():
+        _, values, paths = _arrays(5, 1, log_n, ml, tc)
+        values, paths = np.ascontiguousarray(values[:, 0]), np.ascontiguousarray(paths[:, 0])
+        return ctx.batch_query_round(values=values, paths=paths, **kw)
+
+    one = run()
+    for b in range(5):
+        if skip[b]:
+            assert one[2][b] == 0 and (one[0][b] == VAL_FILL).all() and (one[1][b] == PATH_FILL).all()
+        else:
+            assert one[2][b] >= 32 * log_n * tc + 64 * log_n and not (one[1][b][:one[2][b]] == PATH_FILL).all()
+    try:
+        for chunk in (1, 2, 3):
+            ctx.set_query_chunk(chunk)
+            got = run()
+            assert (got[0] == one[0]).all() and (got[1] == one[1]).all() and got[2] == one[2], chunk
+    finally:
+        ctx.set_query_chunk(0)
+
+
+# ---- 8. the round against the single-proof gather ------------------------------------
+@pytest.mark.parametrize("log_n,ds,indices", [
+    (3, [1, 2, 5, 8], [(1 << 40) + 5] * 4),    # the members differ in layer count; an index far beyond the codeword
+    (1, [2, 2, 2], [0, 1, 5]),                 # the last layer has one element
+])
+def test_round_records_equal_the_members_decommitments(ctx, oracle, log_n, ds, indices):
+    """The round and the phase share one gather kernel, so "phase equals round"
+    does not check the gather itself: fri_batch_decommit_query goes through
+    k_decommit_gather, one member at a time."""
+    polys = [oracle.splitmix64_np(50 + b, d).astype(np.uint32) for b, d in enumerate(ds)]
+    res, _ = _commit(ctx, polys, log_n)
+    nls = [r.n_layers for r in res]
+    if len(set(ds)) > 1:
+        assert len(set(nls)) > 1
+    else:
+        assert nls == [2] * len(ds)
+    values, paths, lens = ctx.batch_query_round(indices)
+    for b, nl in enumerate(nls):
+        assert lens[b] == sum(64 * (log_n - k) for k in range(nl))
+        _, openings = fri_amd.batch_round_records(values[b], paths[b], lens[b], 0, nl, log_n)
+        want = ctx.batch_decommit_query(b, indices[b], nl, log_n)
+        assert len(openings) == nl and openings == want, (b, nl)
+        assert all(len(o[2]) == len(o[3]) == 32 * (log_n - k) for k, o in enumerate(want))

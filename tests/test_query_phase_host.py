@@ -168,3 +168,22 @@ def test_messages_and_take_over_rebuild_a_one_element_last_layer(oracle):
     _rebuild_and_compare(oracle, och, before, pk, 3, log_n, 0, q)
     # the doubled value is there: 1 + 4 + 4 + 5 messages per query
     assert len(och.proof) - len(before.proof) == q * 14
+
+
+def test_record_shape_function_against_the_sums_written_out():
+    """record_paths_len is the mirror's one statement of a query record's
+    paths: trace_count paths of log_n digests, then layer k's two of log_n - k
+    digests.  verify_record_strides is it at max_layers."""
+    for log_n in range(1, 7):
+        for tc in (0, 3):
+            for nl in range(0, log_n + 2):
+                want = 0
+                for _ in range(tc):
+                    want += 32 * log_n
+                for k in range(nl):
+                    want += 32 * (log_n - k)          # the opened element's path
+                    want += 32 * (log_n - k)          # its sibling's
+                assert fri_amd.record_paths_len(log_n, tc, nl) == want, (log_n, tc, nl)
+                hw, vw, pb = fri_amd.verify_record_strides(log_n, nl, tc)
+                assert pb == fri_amd.record_paths_len(log_n, tc, nl) == want
+                assert vw == tc + 2 * nl and hw == (11 if tc else 0) + 9 * nl
